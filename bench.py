@@ -9,16 +9,19 @@ cannot serve repeats. Multi-GPU (config 4): independent blocks shard one set per
 GPU, no collectives on the data path (weak scaling); value = all ranks' payload
 bytes / max-over-ranks time.
 
-Also reported, in the same run:
-  roofline      alg bytes per launch (N*(C+4)) / average launch time
-                from HIP events on the launch stream, vs the 8.0 TB/s HBM peak;
-                `traffic` = DRAM bytes per launch from rocprofv3 PMC passes
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step`
+and `roofline` (alg bytes per launch, N*(C+4), SURVEY.md §8d, over the timed steps' average
+launch time, vs the 8.0 TB/s HBM peak). --dump-outputs DIR also writes what the last timed step
+handed its caller as DIR/<name>.npy (dump_outputs below). Everything else runs only with --full:
+  the oracle gate before timing, the event-bracketed and barriered figures of the pre-passes,
+  the plain-read ceilings, the compute / configs2 / packets / batched / config5 blocks;
+  roofline.traffic  DRAM bytes per launch from rocprofv3 PMC passes
                 (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, separate passes);
   cpu_baseline  the reference CPU path (oracle/_ref HWCrc32c built from the
                 reference sources, else the oracle's crc_pcl restatement) timed on
                 this host on a bounded sample (rank 0, N=1 only).
 
-    python bench.py [--gpus N --steps K --warmup W --bpc 512 --mode verify]
+    python bench.py [--gpus N --steps K --warmup W --bpc 512 --mode verify] [--dump-outputs DIR] [--full]
 
 --gpus N > 1 without a launcher (no WORLD_SIZE in the environment) starts N rank processes
 itself, before anything touches a GPU, exactly as `torch.distributed.run --nproc-per-node N`
@@ -60,6 +63,13 @@ def parse():
     p.add_argument("--mode", choices=["verify", "compute"], default="verify")
     p.add_argument("--block-mib", type=int, default=128)
     p.add_argument("--blocks", type=int, default=8)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the oracle gate, the per-launch and "
+                        "barriered figures, the read ceilings, compute / configs2 / packets / batched / config5, "
+                        "the CPU baseline and the PMC passes (each still has its --no-* switch)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step handed its caller as "
+                        "DIR/<name>.npy (rank 0; see dump_outputs)")
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-pmc", action="store_true")
@@ -302,6 +312,31 @@ def run_steps(work, ctx, mode, n, result, events=None, base=0, overlap=False):
             ctx.compute_dev(dp[b], bb, bpc, cp[b], overlap_previous=overlap and i > 0 and events is None)
         if events is not None:
             events[2 * i + 1].record()
+
+
+def dump_outputs(out_dir, work, mode, K, result):
+    """--dump-outputs: what the last timed step (step K-1 of run_steps, block (K-1) % blocks) handed
+    its caller, as float64 .npy files (every value is an integer below 2^53, so nothing is lost).
+    The blocks come from a seeded generator, so two builds given the same arguments can be compared
+    file by file.
+      verify:  first_bad_chunk.npy   [1]  the step's result word decoded as hdfs3_crc_decode_result
+                                          decodes it: -1 for a clean block, else the chunk index
+               stored_crc_words.npy  [N]  the block's stored CRC32C words the step checked the data
+                                          against (one per chunk; the compute path wrote them during
+                                          set-up), so a clean result is tied to the words themselves
+      compute: crc_words.npy         [N]  the CRC32C words the step wrote, one per chunk
+    At the default shape N = 262,144 (2 MiB per file)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    s = K - 1
+    words = work.crc[s % work.blocks].cpu().numpy().view(">u4").astype(np.float64)
+    if mode == "verify":
+        word = int(result[s % result.numel()].item()) & (2**64 - 1)
+        first_bad = -1 if word == 0 else (~word) & (2**64 - 1)
+        np.save(os.path.join(out_dir, "first_bad_chunk.npy"), np.array([first_bad], dtype=np.float64))
+        np.save(os.path.join(out_dir, "stored_crc_words.npy"), words)
+    else:
+        np.save(os.path.join(out_dir, "crc_words.npy"), words)
 
 
 def batched_rate(torch, work, ctx, mode, reps=100, warm=300):
@@ -1369,8 +1404,8 @@ def main():
     # (round 6): its sender threads are then neither charged to the client's CPU time nor competing
     # inside the client's process unseen
     dn_child = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.mode == "verify" and not args.no_config5 and
-            args.bpc == 512 and not args.pmc_child):
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.mode == "verify" and
+            not args.no_config5 and args.bpc == 512 and not args.pmc_child):
         import atexit
         sys.path.insert(0, os.path.join(REPO, "tests"))
         from loopback import ChildDatanode
@@ -1412,16 +1447,19 @@ def main():
         torch.cuda.synchronize()
         return
 
-    check_against_oracle(work, ctx)
+    if args.full:
+        check_against_oracle(work, ctx)
 
     K, W = args.steps, args.warmup
+    if K < 1:
+        raise SystemExit("--steps must be at least 1")
     result = torch.zeros(max(K, W, 1), dtype=torch.int64, device=device)
-    # (0) diagnostic pass, before the warmup: max(K, 2000) launches eagerly, each bracketed
-    # by HIP events on the launch stream (per-launch duration including dispatch, averaged
-    # over the last K). Running it first also takes the GPU out of its idle power state
-    # (docs/DESIGN_HISTORY.md §5: ~25 ms of load), so short --warmup values still time a steady GPU
+    # (0) pre-pass, before the warmup: max(K, 2000) eager launches. It takes the GPU out of its idle
+    # power state (docs/DESIGN_HISTORY.md §5: ~25 ms of load), so short --warmup values still time a
+    # steady GPU. With --full it is also the diagnostic pass: each launch bracketed by HIP events on
+    # the launch stream (per-launch duration including dispatch, averaged over the last K)
     D = max(K, 2000)
-    events = [torch.cuda.Event(enable_timing=True) for _ in range(2 * D)]
+    events = [torch.cuda.Event(enable_timing=True) for _ in range(2 * D)] if args.full else None
     run_steps(work, ctx, args.mode, D, result, events)
     torch.cuda.synchronize()
     if args.mode == "verify" and bool((result != 0).any().item()):
@@ -1432,18 +1470,22 @@ def main():
     # caller issuing one plain hdfs3_crc32c_verify_dev_async per block gets): max(D - K, 1000)
     # untimed then K timed launches, every one with the AQL barrier bit. It runs before the
     # warmup: together with (0) it keeps the GPU under sustained load for ~100 ms before the
-    # timed region, whatever W is
+    # timed region, whatever W is. A plain run keeps the launches, for that load, and leaves out
+    # their timing and the figure; --full reports it
     barriered = None
     if overlap:
         result.zero_()
         run_steps(work, ctx, args.mode, max(D - K, 1000), result)  # its own untimed warmup
         b0, b1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        b0.record(stream)
+        if args.full:
+            b0.record(stream)
         run_steps(work, ctx, args.mode, K, result)
-        b1.record(stream)
+        if args.full:
+            b1.record(stream)
         torch.cuda.synchronize()
         if bool((result != 0).any().item()):
             raise SystemExit("PARITY FAILURE: clean blocks reported a bad chunk in the barriered pass")
+    if overlap and args.full:
         bl = b0.elapsed_time(b1) * 1e-3 / K
         barriered = {"api": "hdfs3_crc32c_verify_dev_async (AQL barrier bit on every launch)",
                      "value": round(block_bytes / bl / 2**30, 2), "unit": "GiB/s", "ms_per_step": round(bl * 1e3, 4),
@@ -1474,6 +1516,8 @@ def main():
     elapsed = ev0.elapsed_time(ev1) * 1e-3
     if world > 1:
         dist.barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, work, args.mode, K, result)
     if args.mode == "verify" and bool((result != 0).any().item()):
         raise SystemExit("PARITY FAILURE: clean blocks reported a bad chunk in the timed region")
     my_rate = block_bytes * K / elapsed / 2**30
@@ -1496,18 +1540,18 @@ def main():
             dist.destroy_process_group()
         return
 
-    pre_pass = {"diagnostic_event_bracketed": D, "barriered": (max(D - K, 1000) + K) if overlap else 0,
-                "warmup": W}
+    pre_pass = {"diagnostic_event_bracketed" if args.full else "pre_pass": D,
+                "barriered": (max(D - K, 1000) + K) if overlap else 0, "warmup": W}
     pre_pass["total_before_timed_region"] = sum(pre_pass.values())
-    launch_ms = [events[2 * s].elapsed_time(events[2 * s + 1]) for s in range(D)]
-    eager_launch_s = sum(launch_ms[-K:]) / K * 1e-3  # the last K of the diagnostic pass
     avg_launch_s = elapsed / K  # rank 0's own launches, same clock as value
     achieved = alg_bytes / avg_launch_s / 1e9
     roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": None,
                 "alg_bytes_per_launch": alg_bytes, "avg_launch_us": round(avg_launch_s * 1e6, 2),
-                "timing": "HIP events on the launch stream around the K timed steps / K (the clock of value)",
-                "eager_per_launch_us": round(eager_launch_s * 1e6, 2)}
+                "timing": "HIP events on the launch stream around the K timed steps / K (the clock of value)"}
+    if events is not None:
+        launch_ms = [events[2 * s].elapsed_time(events[2 * s + 1]) for s in range(D)]
+        roofline["eager_per_launch_us"] = round(sum(launch_ms[-K:]) / K * 1e3, 2)  # the last K of the diagnostic pass
     if world > 1:
         # the whole job against the whole node's HBM: N x alg bytes x K / max elapsed / (N x 8 TB/s)
         roofline["aggregate_frac"] = round(world * alg_bytes * K / elapsed_max / 1e9 / (world * HBM_PEAK_GBPS), 4)
@@ -1517,7 +1561,8 @@ def main():
     extra = {}
     lab = None
     ceilings = None
-    if world == 1:
+    full1 = args.full and world == 1  # everything below but the line itself: --full, one rank
+    if full1:
         try:
             lab = lab_context(work, stream)
             whole, per_block, best_grid = stream_read_ceiling(torch, work, lab, overlap=overlap)
@@ -1572,14 +1617,14 @@ def main():
             raise
         except Exception as e:
             log("batched pass failed:", e)
-    if world == 1 and args.mode == "verify" and not args.no_config5 and args.bpc == 512:
+    if full1 and args.mode == "verify" and not args.no_config5 and args.bpc == 512:
         extra["config5"] = config5_block(torch, device, host_data, args.bpc, block_bytes, reps=5, dn=dn_child)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if full1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(work, args.cpu_seconds, args.bpc, data=host_data)
-    if args.sweep and world == 1 and lab is not None:
+    if args.sweep and full1 and lab is not None:
         log(json.dumps({"lane_read_GBps": round(lane_read_rate(torch, work, lab), 1)}))
-    if world == 1 and not args.no_pmc:
+    if full1 and not args.no_pmc:
         traffic, note = pmc_traffic(args)
         roofline["traffic"] = int(traffic) if traffic else None
         roofline["traffic_note"] = note

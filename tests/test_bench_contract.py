@@ -16,7 +16,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(320)  # the verify line carries configs[2] and configs[4] too (~1 min on the box)
 @pytest.mark.parametrize("mode", ["verify", "compute"])
 def test_bench_json_line(mode):
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "50", "--warmup", "10", "--no-pmc",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "50", "--warmup", "10", "--no-pmc",
            "--no-cpu-baseline", "--mode", mode]
     out = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -75,3 +75,46 @@ def test_bench_json_line(mode):
     wb = j["packets"]["writer_batch"]
     assert wb["chunks_per_packet"] == 127 and wb["packet_data_bytes"] == 65024 and wb["packets_per_batch"] == 64
     assert wb["compute_us"] > 0 and 0 < wb["compute_frac"] < 1 and wb["reader_dense_us"] > 0
+
+
+FULL_ONLY = ("barriered", "batched", "packets", "compute", "configs2", "config5", "gpu_over_cpu")
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the bench only sets up, warms up, times its K steps and prints the line: the
+    headline fields and the roofline of the timed steps, none of the side measurements. --dump-outputs
+    writes what the last timed step (step 6 of 7: block 6 % 2 = 0) handed its caller. The blocks are
+    seeded: the words a compute run writes for that block are the stored words a verify run, another
+    process, checked it against (the words themselves meet the oracle in the --full run above)."""
+    import numpy as np
+
+    got = {}
+    for mode, names in (("verify", ["first_bad_chunk.npy", "stored_crc_words.npy"]), ("compute", ["crc_words.npy"])):
+        out_dir = tmp_path / mode
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+               "--blocks", "2", "--block-mib", "4", "--mode", mode, "--dump-outputs", str(out_dir)]
+        out = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 7 and j["warmup"] == 3 and j["n_gpus"] == 1 and j["config"]["mode"] == mode
+        assert j["unit"] == "GiB/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+        # one clock: value is one block over ms_per_step (which carries 4 decimals)
+        assert j["ms_per_step"] > 0
+        assert j["value"] == pytest.approx((4 << 20) / (j["ms_per_step"] * 1e-3) / 2**30,
+                                           rel=0.6e-4 / j["ms_per_step"] + 1e-3)
+        assert j["roofline"]["alg_bytes_per_launch"] == (4 << 20) // 512 * 516 and 0 < j["roofline"]["frac"] <= 1
+        assert j["cpu_baseline"] is None and j["roofline"]["traffic"] is None
+        for key in FULL_ONLY:
+            assert key not in j, key
+        assert sorted(os.listdir(out_dir)) == names
+        for n in names:
+            got[n] = np.load(out_dir / n)
+            assert got[n].dtype == np.float64, n
+    assert got["first_bad_chunk.npy"].tolist() == [-1.0]
+    words = got["crc_words.npy"]
+    assert words.shape == ((4 << 20) // 512,) and np.array_equal(words, got["stored_crc_words.npy"])
+    assert np.all(words == np.floor(words)) and words.min() >= 0 and words.max() < 2**32
+    assert len(np.unique(words)) > words.size // 2  # CRCs of random chunks, not a constant fill
