@@ -98,11 +98,8 @@ struct Batch {
     }
 };
 
-// Chunk sizes the contiguous round kernels take (launch_chunks): 512 ... 4096, and R x 4096 (the
-// multi-round kernel / pieces + combine). Others keep the wire layout and the chunk-per-lane kernel.
-bool dense_bpc(uint32_t bpc) {
-    return bpc == 512 || bpc == 1024 || bpc == 2048 || bpc == 4096 || (bpc > 4096 && bpc % 4096 == 0);
-}
+// Chunk sizes the contiguous kernels take (launch_chunks); others keep the wire layout
+bool dense_bpc(uint32_t bpc) { return round_bpc(bpc) || pieces_bpc(bpc); }
 
 // HDFS3_READER_LAYOUT=wire keeps every batch in the wire layout (A/B measurement knob)
 bool wire_layout_forced() {
@@ -439,7 +436,10 @@ struct hdfs3_block_reader {
             b.verified = true;
             return 0;
         }
-        const uint32_t *fold = ctx->d_fold_by[tables == ctx->d_tables_by[1]];
+        // this reader's own polynomial (the ctx's active tables may differ) and the batch's own piece scratch
+        LaunchEnv env = launch_env(ctx, &b.a.pieces);
+        env.tables = tables;
+        env.fold = ctx->d_fold_by[tables == ctx->d_tables_by[1]];
         HIP_OK(hipMemcpyAsync(b.a.d, b.a.h, b.used, hipMemcpyHostToDevice, ctx->stream));
         HIP_OK(hipMemsetAsync(b.a.d_res, 0, sizeof(unsigned long long), ctx->stream));
         if (b.dense) {
@@ -453,14 +453,13 @@ struct hdfs3_block_reader {
             a.crc_be = b.a.d;
             a.result = b.a.d_res;
             a.check_short_tail = 0;  // verifyChecksum ignores a short chunk's mismatch (:319)
-            HIP_OK(launch_chunks(a, true, tables, fold, ctx->grid_cap, ctx->stream, &b.a.pieces));
+            HIP_OK(launch_chunks(env, a, true));
         } else {
             std::vector<DevPacket> hp(b.pk.size());
             for (size_t i = 0; i < b.pk.size(); ++i)
                 hp[i] = DevPacket{b.pk[i].data_off, b.pk[i].crc_off, b.pk[i].data_len, 0};
-            HIP_OK(launch_packet_batch(b.a.d, hp.data(), hp.size(), chunk_size, true, /*check_short_tail=*/0, b.a.d_res,
-                                       b.a.h_desc, b.a.d_desc, tables, fold, ctx->grid_cap, ctx->stream, 0, nullptr,
-                                       false, nullptr, &b.a.pieces));
+            HIP_OK(launch_packet_batch(env, b.a.d, hp.data(), hp.size(), chunk_size, true, /*check_short_tail=*/0,
+                                       b.a.d_res, b.a.h_desc, b.a.d_desc));
         }
         ++ctx->launches;
         HIP_OK(hipMemcpyAsync(b.a.h_res, b.a.d_res, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));

@@ -296,7 +296,6 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_chunks_kernel(ChunkLaunc
 // For bpc a multiple of 4096 a wave walks the chunk's rounds in order and folds
 // round results with the uniform 4096-byte advance.
 
-constexpr int kRoundBytes = 4096;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
 
 struct Round {
@@ -347,7 +346,6 @@ __device__ __forceinline__ void load_round_buf(Round &r, const uint8_t *base, ui
         r.w[t][3] = v.w;
     }
 }
-
 
 __device__ __forceinline__ void swap32(uint32_t &a, uint32_t &b) {
     const auto p = __builtin_amdgcn_permlane32_swap(a, b, false, false);
@@ -639,7 +637,6 @@ __device__ __forceinline__ uint32_t fold_half(const uint8_t *lds, uint32_t x) {
 }
 
 // ---- segment lists (blocks of a batch, packets): crc32c_segments_kernel, crc32c_wave.h ----
-constexpr uint32_t kInlineSegments = 16;  // small lists travel in the kernel arguments
 
 struct SegLaunch {
     const DevSegment *seg;  // device array, or nullptr: use inl[] (nseg <= kInlineSegments)

@@ -10,8 +10,8 @@ namespace hdfs3crc {
 namespace {
 
 template <int BPC, bool V>
-hipError_t launch_exp(int variant, const ChunkLaunch &a, const uint32_t *tab, const uint32_t *fold, int grid_cap,
-                      hipStream_t s) {
+hipError_t launch_exp(const LaunchEnv &env, int variant, const ChunkLaunch &a) {
+    const auto [tab, fold, grid_cap, s] = std::tie(env.tables, env.fold, env.grid_cap, env.stream);
     if constexpr (BPC > kRoundBytes) {
         if (variant == 115) return launch_r3<BPC, V, 1, true, true>(a, tab, fold, grid_cap, s);  // s_setprio
         if (variant == 123) return launch_r3<BPC, V, 1, true>(a, tab, fold, grid_cap, s);  // multi-round kernel
@@ -84,27 +84,12 @@ hipError_t launch_exp(int variant, const ChunkLaunch &a, const uint32_t *tab, co
     return hipErrorInvalidValue;
 }
 
-template <int BPC>
-hipError_t launch_exp_v(int variant, const ChunkLaunch &a, bool verify, const uint32_t *tab, const uint32_t *fold,
-                        int grid_cap, hipStream_t s) {
-    return verify ? launch_exp<BPC, true>(variant, a, tab, fold, grid_cap, s)
-                  : launch_exp<BPC, false>(variant, a, tab, fold, grid_cap, s);
-}
-
 }  // namespace
 
-hipError_t launch_experiment(int variant, const ChunkLaunch &a, bool verify, const uint32_t *tab,
-                             const uint32_t *fold, int grid_cap, hipStream_t s) {
-    switch (a.bpc) {
-    case 512: return launch_exp_v<512>(variant, a, verify, tab, fold, grid_cap, s);
-    case 1024: return launch_exp_v<1024>(variant, a, verify, tab, fold, grid_cap, s);
-    case 2048: return launch_exp_v<2048>(variant, a, verify, tab, fold, grid_cap, s);
-    case 4096: return launch_exp_v<4096>(variant, a, verify, tab, fold, grid_cap, s);
-    case 8192: return launch_exp_v<8192>(variant, a, verify, tab, fold, grid_cap, s);
-    case 16384: return launch_exp_v<16384>(variant, a, verify, tab, fold, grid_cap, s);
-    case 65536: return launch_exp_v<65536>(variant, a, verify, tab, fold, grid_cap, s);
-    default: return hipErrorInvalidValue;
-    }
+hipError_t launch_experiment(const LaunchEnv &env, int variant, const ChunkLaunch &a, bool verify) {
+    return dispatch_bpc<true>(a.bpc, [&](auto bpc) {
+        return verify ? launch_exp<bpc(), true>(env, variant, a) : launch_exp<bpc(), false>(env, variant, a);
+    });
 }
 
 void set_variant(int v) { g_variant = v; }

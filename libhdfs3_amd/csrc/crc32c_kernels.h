@@ -2,10 +2,12 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
-#include <cstddef>
-#include <cstdint>
 
 #include <atomic>
+#include <tuple>
+#include <type_traits>
+
+#include "launch_plan.h"
 
 namespace hdfs3crc {
 
@@ -13,25 +15,6 @@ namespace hdfs3crc {
 // the CU's 160 KiB LDS, so one workgroup owns a CU; 1024 threads = 16 waves
 // (4 per SIMD) keep the CU's memory pipe and LDS busy.
 constexpr int kBlockThreads = 1024;
-
-// The 4 KiB units of a packet stream (PitchWalk, crc32c_wave.h). A packet of whole chunks is
-// ceil(bytes / 4096) units; its last unit may be PARTIAL (the writer's 127-chunk packets at bpc
-// 512: 65,024 B = 15 whole rounds + 3,584 B, OutputStreamImpl.cpp:161-170): its loads are bounded by
-// a buffer resource of ptail bytes, so the lanes past the last whole chunk read zeros and their
-// results are dropped. Unit u -> packet u / upp by a multiply-shift (u < 2^31: q = (u * magic) >>
-// shift, Granlund-Montgomery with N = 31), so upp need not be a power of two.
-struct PacketGeom {
-    uint64_t pk_len = 0;  // data bytes of every packet but the last (whole chunks)
-    uint32_t upp = 0;     // units per packet but the last
-    uint32_t magic = 0, shift = 0;
-    uint32_t ptail = 0;   // valid bytes of such a packet's last unit (4096: whole)
-    uint32_t lunits = 0;  // units of the last packet (its whole chunks only)
-    uint32_t ltail = 0;   // valid bytes of the last packet's last unit
-};
-// Fills g for npk packets of data_len bytes (the last last_len) with chunks of unit_bpc bytes
-// (<= 4096; callers at bpc = R x 4096 pass 4096). False when it does not fit the walk: a non-last
-// packet that ends in a short chunk, no unit at all, or 2^31 units or more.
-bool packet_geom(uint64_t data_len, uint64_t last_len, uint64_t npk, uint32_t unit_bpc, PacketGeom *g);
 
 struct ChunkLaunch {
     const uint8_t *data;      // device pointer to the first chunk
@@ -63,55 +46,23 @@ struct ChunkLaunch {
 // lab clock stamps: launches numbered by the host (kernel argument), see LabClock
 inline std::atomic<uint32_t> g_lab_seq{0};
 
-// Packet-descriptor as seen by the device (mirrors hdfs3_pkt_desc).
-struct DevPacket {
-    uint64_t data_off;
-    uint64_t crc_off;
-    uint32_t data_len;
-    uint32_t reserved;
-};
+// The launch of a planned pitch stream whose first packet's data and words are at data / crc
+inline ChunkLaunch pitch_stream_launch(const PitchStream &s, const uint8_t *data, uint8_t *crc, uint32_t bpc,
+                                       int check_short_tail, unsigned long long *result) {
+    ChunkLaunch a{};
+    a.data = data;
+    a.crc_be = a.out_be = crc;
+    a.bpc = bpc;
+    a.result = result;
+    a.check_short_tail = check_short_tail;
+    a.pitch = s.pitch;
+    a.crc_pitch = s.crc_pitch;
+    a.npk = s.npk;
+    a.geom = s.geom;
+    a.last_len = s.last_len;
+    return a;
+}
 
-// One independent byte range of a segmented launch (a block of a batch, or one packet's
-// data region): device pointers, its 4 KiB units start at global unit unit_begin,
-// chunk c of it is reported as key_base + c (packets: packet << 32).
-struct DevSegment {
-    const uint8_t *data;
-    uint8_t *crc;            // verify: stored BE32 words; compute: written here
-    uint64_t len;
-    uint64_t unit_begin;
-    uint64_t key_base;
-};
-
-// Units of a segment of len bytes at bpc <= 4096: its whole chunks cut into 4 KiB units, the
-// last one partial when the whole chunks end inside a round (PacketGeom); a short last chunk is
-// the kernel's one-lane tail
-constexpr uint64_t seg_units(uint64_t len, uint32_t bpc) { return (len / bpc * bpc + 4095) / 4096; }
-
-// Fills h_seg for n segments (data/crc/len/key_base already set) and returns the total
-// unit count (seg_units); *uniform = units per segment when every segment but the last has
-// the same count (direct unit -> segment mapping), else 0 (binary search).
-uint64_t plan_segments(DevSegment *h_seg, size_t n, uint32_t bpc, uint64_t *uniform);
-// True when the segmented wave kernel can take these segments: bpc in {512..4096},
-// every data pointer 16-byte aligned and every CRC pointer 4-byte aligned.
-bool segments_fast(const DevSegment *h_seg, size_t n, uint32_t bpc);
-// Launches over d_seg (a device copy of a planned h_seg array), or, with h_inline and
-// nseg <= 16, over descriptors carried in the kernel arguments (no copy before the kernel).
-hipError_t launch_segments(const DevSegment *d_seg, uint32_t nseg, uint64_t units, uint64_t uniform,
-                           uint32_t bpc, bool verify, int check_short_tail, unsigned long long *result,
-                           const uint32_t *d_tables, const uint32_t *d_fold, int grid_cap, hipStream_t stream,
-                           const DevSegment *h_inline = nullptr, uint64_t stride = 0,
-                           uint8_t *dense_words = nullptr, const uint32_t *unit_seg = nullptr);
-constexpr uint32_t kMaxInlineSegments = 16;
-
-// Packet batch (packets API, block reader, output stream): descriptors in host memory;
-// h_stage/d_stage are pinned/device staging for n DevSegments. Uses the segmented wave
-// kernel when segments_fast() holds, else the chunk-per-lane packet kernel. Keys are
-// (packet << 32 | chunk).
-// constant-pitch packet streams (ChunkLaunch::pitch): whether the wave kernel's pitch mode
-// takes them (bpc 512..4096 or R x 4096, aligned, every packet but the last whole chunks), and
-// its launcher (a.pitch/npk/geom/last_len set)
-bool packet_stream_ok(uint64_t data_len, uint64_t last_len, uint64_t npk, uint32_t bpc, const void *data,
-                      const void *crc, uint64_t pitch, PacketGeom *geom);
 // Compute mode over a stream whose CRC words sit inside each packet (the wire layout: 512 B of
 // words per 64 KiB packet, 66 KiB apart) writes 8 MiB per GiB as small regions scattered over
 // the arena, interleaved with the read stream: 1 GiB took 213 us against 186 us with the words
@@ -127,14 +78,6 @@ struct WordScratch {
 // kernel computes the CRC of every 4096-byte piece into a ctx-owned scratch (two buffers used in
 // turn, so a launch that overlaps its predecessor never writes the words that predecessor's combine
 // still reads), then a combine kernel folds each chunk's R piece CRCs (launch_chunks, pieces != null).
-// Where a long descriptor list's host-to-device copy runs (round 6): on `side`, beside the launch before
-// it, with `stream` waiting for `copied`; in `stream` itself when null or below kSideCopyMinBytes
-struct DescCopy {
-    hipStream_t side = nullptr;
-    hipEvent_t copied = nullptr;
-};
-constexpr size_t kSideCopyMinBytes = size_t(256) << 10;
-
 struct PieceScratch {
     uint8_t *d[2] = {nullptr, nullptr};
     uint64_t cap[2] = {0, 0};
@@ -143,40 +86,71 @@ struct PieceScratch {
     unsigned next = 0;
     void release();
 };
+// Where a long descriptor list's host-to-device copy runs (round 6): on `side`, beside the launch before
+// it, with `stream` waiting for `copied`; in `stream` itself when null or below kSideCopyMinBytes
+struct DescCopy {
+    hipStream_t side = nullptr;
+    hipEvent_t copied = nullptr;
+};
 
-// word regions at most this long (per packet) take the dense path: 64 KiB = 8 MiB packets at bpc 512
-constexpr uint64_t kDenseWordsMaxRegion = 64 * 1024;
-// pieces != null: streams at bpc = R * 4096 (R dividing the rounds per packet) take the piece
-// CRCs + combine (round 4); without it they return hipErrorNotSupported (the caller's fallback)
-hipError_t launch_packet_stream(const ChunkLaunch &a, bool verify, const uint32_t *d_tables, const uint32_t *d_fold,
-                                int grid_cap, hipStream_t stream, WordScratch *ws = nullptr,
-                                PieceScratch *pieces = nullptr);
-// batches of equal blocks (the last may be shorter) of a power-of-two number of whole rounds
-// whose data and words sit at two constant strides (blocks of one 2-D tensor): the pitch mode
-// with crc_pitch; hipErrorNotSupported = use the segmented kernel
-hipError_t launch_strided_blocks(const DevSegment *h_seg, size_t n, uint32_t bpc, bool verify, int check_short_tail,
-                                 unsigned long long *result, const uint32_t *d_tables, const uint32_t *d_fold,
-                                 int grid_cap, hipStream_t stream, WordScratch *ws = nullptr);
+// What every launcher needs beyond its work (launch_env, ctx.h)
+struct LaunchEnv {
+    const uint32_t *tables = nullptr, *fold = nullptr;  // slice-table image, lane-fold GF(2) matrices (device)
+    int grid_cap = 0;
+    hipStream_t stream = nullptr;
+    WordScratch *words = nullptr;          // null: compute writes its words in place
+    PieceScratch *pieces = nullptr;        // null: no pieces + combine, no unit map
+    const DescCopy *desc_copy = nullptr;   // null: descriptors copy in `stream`
+};
+
+// f(std::integral_constant<int, BPC>) for the chunk sizes that have a kernel of their own: the round
+// kernel's, and with kMultiRound the multi-round kernel's; hipErrorInvalidValue for every other bpc
+template <bool kMultiRound = false, class F>
+hipError_t dispatch_bpc(uint32_t bpc, F &&f) {
+    switch (bpc) {
+    case 512: return f(std::integral_constant<int, 512>());
+    case 1024: return f(std::integral_constant<int, 1024>());
+    case 2048: return f(std::integral_constant<int, 2048>());
+    case 4096: return f(std::integral_constant<int, 4096>());
+    default: break;
+    }
+    if constexpr (kMultiRound) {
+        if (bpc == 8192) return f(std::integral_constant<int, 8192>());
+        if (bpc == 16384) return f(std::integral_constant<int, 16384>());
+        if (bpc == 65536) return f(std::integral_constant<int, 65536>());
+    }
+    return hipErrorInvalidValue;
+}
+
+// One contiguous block: the round, the multi-round or (unaligned, short, other bpc) the chunk-per-lane kernel
+hipError_t launch_chunks(const LaunchEnv &env, const ChunkLaunch &a, bool verify);
+
+// A planned constant-pitch packet stream (pitch_stream_launch): the pitch walk; compute goes through
+// env.words when the words sit inside the packets; bpc = R x 4096: pieces in env.pieces + the combine
+hipError_t launch_packet_stream(const LaunchEnv &env, const ChunkLaunch &a, bool verify);
+
+// Launches over d_seg (a device copy of a planned h_seg array), or, with h_inline and
+// nseg <= kInlineSegments, over descriptors carried in the kernel arguments (no copy before the
+// kernel); stride != 0: h_inline = {first, last} and the kernel derives the rest (SegLaunch::stride)
+hipError_t launch_segments(const LaunchEnv &env, const DevSegment *d_seg, uint32_t nseg, uint64_t units,
+                           uint64_t uniform, uint32_t bpc, bool verify, int check_short_tail,
+                           unsigned long long *result, const DevSegment *h_inline = nullptr, uint64_t stride = 0,
+                           uint8_t *dense_words = nullptr, const uint32_t *unit_seg = nullptr);
+
+// The chunk-per-lane packet kernel over a device array of descriptors: one wave per packet
+hipError_t launch_packets(const LaunchEnv &env, const uint8_t *d_arena, const DevPacket *d_pk, uint64_t n,
+                          uint32_t bpc, bool verify, int check_short_tail, unsigned long long *result);
+
+// Packet batch (packets API, block reader, output stream): descriptors in host memory; h_stage/d_stage are pinned/
+// device staging for n DevSegments. plan_packet_batch picks the route, this launches it. Keys: packet << 32 | chunk.
 // bad_index != null: every packet is first checked against [0, arena_len) (hipErrorInvalidValue
 // and *bad_index = the first one outside). staged != null: set when the launch copies h_stage to the
 // device asynchronously (the caller may reuse h_stage only after that copy ran); false when the
 // kernel's arguments carried everything (the pitch walk, inline descriptors).
-hipError_t launch_packet_batch(const uint8_t *d_arena, const DevPacket *h_pk, size_t n, uint32_t bpc, bool verify,
-                               int check_short_tail, unsigned long long *result, DevSegment *h_stage,
-                               DevSegment *d_stage, const uint32_t *d_tables, const uint32_t *d_fold, int grid_cap,
-                               hipStream_t stream, uint64_t arena_len = 0, size_t *bad_index = nullptr,
-                               bool overlap_previous = false, WordScratch *ws = nullptr,
-                               PieceScratch *pieces = nullptr, bool *staged = nullptr,
-                               const DescCopy *dc = nullptr);
-
-hipError_t launch_chunks(const ChunkLaunch &a, bool verify, const uint32_t *d_tables,
-                         const uint32_t *d_fold, int grid_cap, hipStream_t stream,
-                         PieceScratch *pieces = nullptr);
-
-hipError_t launch_packets(const uint8_t *d_arena, const DevPacket *d_pk, uint64_t n,
-                          uint32_t bpc, bool verify, int check_short_tail,
-                          unsigned long long *result, const uint32_t *d_tables, int grid_cap,
-                          hipStream_t stream);
+hipError_t launch_packet_batch(const LaunchEnv &env, const uint8_t *d_arena, const DevPacket *h_pk, size_t n,
+                               uint32_t bpc, bool verify, int check_short_tail, unsigned long long *result,
+                               DevSegment *h_stage, DevSegment *d_stage, uint64_t arena_len = 0,
+                               size_t *bad_index = nullptr, bool overlap_previous = false, bool *staged = nullptr);
 
 // HDFS3_LAB=1 builds the measurement library (libhdfs3_crc_lab.so: tools/, the A/B tests):
 // the same production launchers plus a process-wide kernel-variant knob, the kernel
@@ -195,8 +169,7 @@ hipError_t lab_clock_buffer(unsigned long long *d, unsigned int cap, unsigned in
 // previous one
 hipError_t lab_wave_buffer(unsigned long long *d, unsigned int cap, unsigned int *n_out);
 // The A/B variants (crc32c_experiments.hip): variant != 0, bpc with a whole-round kernel.
-hipError_t launch_experiment(int variant, const ChunkLaunch &a, bool verify, const uint32_t *tab,
-                             const uint32_t *fold, int grid_cap, hipStream_t s);
+hipError_t launch_experiment(const LaunchEnv &env, int variant, const ChunkLaunch &a, bool verify);
 
 // Measurement-only kernels (bench/profiling): HBM read ceiling and the CRC
 // kernel's access pattern without the table arithmetic.

@@ -140,3 +140,12 @@ struct hdfs3_crc_ctx {
     std::vector<hdfs3crc::PacketArena> arena_cache;
 };
 
+namespace hdfs3crc {
+// A ctx's launch environment. own_pieces: a batch arena's piece scratch (block reader, output stream), whose
+// launches may come from another thread and so leave the ctx's own word and piece scratch alone
+inline LaunchEnv launch_env(hdfs3_crc_ctx *ctx, PieceScratch *own_pieces = nullptr) {
+    return LaunchEnv{ctx->d_tables, ctx->d_fold, ctx->grid_cap, ctx->stream, own_pieces ? nullptr : &ctx->words,
+                     own_pieces ? own_pieces : &ctx->pieces, nullptr};
+}
+}  // namespace hdfs3crc
+

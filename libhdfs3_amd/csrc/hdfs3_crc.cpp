@@ -149,9 +149,8 @@ int finish_pending(Slot &s) {
     return 0;
 }
 
-int launch(hdfs3_crc_ctx *ctx, const ChunkLaunch &in, bool verify) {
-    ChunkLaunch a = in;
-    HIP_TRY(launch_chunks(a, verify, ctx->d_tables, ctx->d_fold, ctx->grid_cap, ctx->stream, &ctx->pieces));
+int launch(hdfs3_crc_ctx *ctx, const ChunkLaunch &a, bool verify) {
+    HIP_TRY(launch_chunks(launch_env(ctx), a, verify));
     ++ctx->launches;
     return 0;
 }
@@ -264,15 +263,16 @@ int packets_async(hdfs3_crc_ctx *ctx, const uint8_t *d_arena, size_t arena_len, 
     // a long list's descriptors copy on the ctx's side stream, under the launch before (the slot's
     // host and device halves are free: stage_segments waited for its last launch)
     DescCopy dc;
+    LaunchEnv env = launch_env(ctx);
     if (n * sizeof(DevSegment) >= kSideCopyMinBytes) {
         if (!ctx->desc_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->desc_stream, hipStreamNonBlocking));
         if (!st->copied) HIP_TRY(hipEventCreateWithFlags(&st->copied, hipEventDisableTiming));
         dc.side = ctx->desc_stream;
         dc.copied = st->copied;
+        env.desc_copy = &dc;
     }
-    const hipError_t e = launch_packet_batch(d_arena, hp, n, bpc, verify, check_short_tail, d_result, st->h, st->d,
-                                             ctx->d_tables, ctx->d_fold, ctx->grid_cap, ctx->stream, arena_len,
-                                             &bad, overlap, &ctx->words, &ctx->pieces, &staged, &dc);
+    const hipError_t e = launch_packet_batch(env, d_arena, hp, n, bpc, verify, check_short_tail, d_result, st->h, st->d,
+                                             arena_len, &bad, overlap, &staged);
     if (e == hipErrorInvalidValue) return fail(-EINVAL, "packet %zu lies outside the %zu-byte arena", bad, arena_len);
     HIP_TRY(e);
     ++ctx->launches;
@@ -324,29 +324,15 @@ int packet_stream_async(hdfs3_crc_ctx *ctx, const uint8_t *d_arena, size_t arena
         ps->crc_off + 4 * (ps->n > 1 ? chunks : lchunks) > arena_len || lc + 4 * lchunks > arena_len ||
         (ps->n > 1 && ps->pitch == 0))
         return fail(-EINVAL, "the packet stream does not fit the %zu-byte arena", arena_len);
-    PacketGeom geom;
-    if (packet_stream_ok(ps->data_len, ps->last_len, ps->n, bpc, d_arena + ps->data_off, d_arena + ps->crc_off,
-                         ps->pitch, &geom)) {
-        ChunkLaunch a{};
-        a.data = d_arena + ps->data_off;
-        a.crc_be = d_arena + ps->crc_off;
-        a.out_be = const_cast<uint8_t *>(d_arena) + ps->crc_off;
-        a.bpc = bpc;
-        a.result = d_result;
-        a.check_short_tail = check_short_tail;
-        a.pitch = ps->pitch;
-        a.npk = ps->n;
-        a.geom = geom;
-        a.last_len = ps->last_len;
+    PitchStream s;
+    if (plan_packet_stream(ps->data_len, ps->last_len, ps->n, bpc, d_arena + ps->data_off, d_arena + ps->crc_off,
+                           ps->pitch, /*have_pieces=*/true, g_variant, &s)) {
+        ChunkLaunch a = pitch_stream_launch(s, d_arena + ps->data_off, const_cast<uint8_t *>(d_arena) + ps->crc_off, bpc,
+                                            check_short_tail, d_result);
         a.overlap_previous = overlap && verify;
-        const hipError_t e =
-            launch_packet_stream(a, verify, ctx->d_tables, ctx->d_fold, ctx->grid_cap, ctx->stream, &ctx->words,
-                                 &ctx->pieces);
-        if (e != hipErrorNotSupported) {
-            HIP_TRY(e);
-            ++ctx->launches;
-            return 0;
-        }
+        HIP_TRY(launch_packet_stream(launch_env(ctx), a, verify));
+        ++ctx->launches;
+        return 0;
     }
     std::vector<hdfs3_pkt_desc> pk(ps->n);
     for (uint64_t i = 0; i < ps->n; ++i)
@@ -389,21 +375,21 @@ int blocks_common(hdfs3_crc_ctx *ctx, const hdfs3_dev_block *blocks, size_t n, u
                               blocks[i].len, 0, uint64_t(i) << 32};
     // blocks of one 2-D tensor (constant data and word strides, equal whole-round blocks): the
     // wave kernel walks them directly (pitch mode); everything else: the segmented kernel
-    const hipError_t te = launch_strided_blocks(st->h, n, bpc, verify, check_short_tail, d_result, ctx->d_tables,
-                                                ctx->d_fold, ctx->grid_cap, ctx->stream, &ctx->words);
-    if (te != hipErrorNotSupported) {
-        HIP_TRY(te);
+    const LaunchEnv env = launch_env(ctx);
+    PitchStream s;
+    if (plan_strided_blocks(st->h, n, bpc, g_variant, &s)) {
+        HIP_TRY(launch_packet_stream(
+            env, pitch_stream_launch(s, st->h[0].data, st->h[0].crc, bpc, check_short_tail, d_result), verify));
         ++ctx->launches;
     } else if (segments_fast(st->h, n, bpc)) {
         uint64_t uniform = 0;
         const uint64_t units = plan_segments(st->h, n, bpc, &uniform);
-        if (n <= kMaxInlineSegments) {  // descriptors in the kernel arguments: no copy first
-            HIP_TRY(launch_segments(nullptr, uint32_t(n), units, uniform, bpc, verify, check_short_tail, d_result,
-                                    ctx->d_tables, ctx->d_fold, ctx->grid_cap, ctx->stream, st->h));
+        if (n <= kInlineSegments) {  // descriptors in the kernel arguments: no copy first
+            HIP_TRY(launch_segments(env, nullptr, uint32_t(n), units, uniform, bpc, verify, check_short_tail, d_result,
+                                    st->h));
         } else {
             HIP_TRY(hipMemcpyAsync(st->d, st->h, n * sizeof(DevSegment), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(launch_segments(st->d, uint32_t(n), units, uniform, bpc, verify, check_short_tail, d_result,
-                                    ctx->d_tables, ctx->d_fold, ctx->grid_cap, ctx->stream));
+            HIP_TRY(launch_segments(env, st->d, uint32_t(n), units, uniform, bpc, verify, check_short_tail, d_result));
             // the pinned staging is read by the copy: reusable once it ran. The other paths read
             // it on the host only (the launch's arguments carry what the kernel needs), and an
             // event between launches costs a marker packet (~4 us of idle between barriered

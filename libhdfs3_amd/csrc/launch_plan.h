@@ -1,0 +1,123 @@
+// Launch planning of the CRC kernels' host layer: which kernel a packet stream, a block batch or a
+// packet batch takes, and that launch's geometry. Plain host arithmetic, no GPU runtime
+// (tests/native/launch_plan_check.cpp); crc32c_kernels.hip turns a plan into launches.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace hdfs3crc {
+
+constexpr int kRoundBytes = 4096;         // a wave's round: 64 lanes x 64 bytes
+constexpr uint32_t kInlineSegments = 16;  // small segment lists travel in the kernel arguments
+// Lists longer than this take the unit map (below it the search is a few loads and the map's launch
+// is not worth it)
+constexpr size_t kUnitMapMinSegments = 256;
+// word regions at most this long (per packet) take the dense path: 64 KiB = 8 MiB packets at bpc 512
+constexpr uint64_t kDenseWordsMaxRegion = 64 * 1024;
+constexpr uint64_t kPiecesMinBytes = uint64_t(256) << 20;  // launch_chunks: pieces + combine at 8 / 16 / 64 KiB
+constexpr size_t kSideCopyMinBytes = size_t(256) << 10;    // descriptor lists that copy on the side stream (DescCopy)
+
+// the round kernel's chunk sizes (a chunk is G = bpc / 64 lanes of one round)
+constexpr bool round_bpc(uint32_t bpc) { return bpc == 512 || bpc == 1024 || bpc == 2048 || bpc == 4096; }
+// chunks of R >= 2 whole rounds: 4096-byte piece CRCs + a combine
+constexpr bool pieces_bpc(uint32_t bpc) { return bpc > uint32_t(kRoundBytes) && bpc % kRoundBytes == 0; }
+
+// The 4 KiB units of a packet stream (PitchWalk, crc32c_wave.h). A packet of whole chunks is
+// ceil(bytes / 4096) units; its last unit may be PARTIAL (the writer's 127-chunk packets at bpc
+// 512: 65,024 B = 15 whole rounds + 3,584 B, OutputStreamImpl.cpp:161-170): its loads are bounded by
+// a buffer resource of ptail bytes, so the lanes past the last whole chunk read zeros and their
+// results are dropped. Unit u -> packet u / upp by a multiply-shift (u < 2^31: q = (u * magic) >>
+// shift, Granlund-Montgomery with N = 31), so upp need not be a power of two.
+struct PacketGeom {
+    uint64_t pk_len = 0;  // data bytes of every packet but the last (whole chunks)
+    uint32_t upp = 0;     // units per packet but the last
+    uint32_t magic = 0, shift = 0;
+    uint32_t ptail = 0;   // valid bytes of such a packet's last unit (4096: whole)
+    uint32_t lunits = 0;  // units of the last packet (its whole chunks only)
+    uint32_t ltail = 0;   // valid bytes of the last packet's last unit
+};
+// Fills g for npk packets of data_len bytes (the last last_len) with chunks of unit_bpc bytes
+// (<= 4096; callers at bpc = R x 4096 pass 4096). False when it does not fit the walk: a non-last
+// packet that ends in a short chunk, no unit at all, or 2^31 units or more.
+// Open finding: npk == 1 with last_len above one round gets upp = 1.
+bool packet_geom(uint64_t data_len, uint64_t last_len, uint64_t npk, uint32_t unit_bpc, PacketGeom *g);
+
+// Packet-descriptor as seen by the device (mirrors hdfs3_pkt_desc).
+struct DevPacket {
+    uint64_t data_off;
+    uint64_t crc_off;
+    uint32_t data_len;
+    uint32_t reserved;
+};
+
+// One independent byte range of a segmented launch (a block of a batch, or one packet's
+// data region): device pointers, its 4 KiB units start at global unit unit_begin,
+// chunk c of it is reported as key_base + c (packets: packet << 32).
+struct DevSegment {
+    const uint8_t *data;
+    uint8_t *crc;            // verify: stored BE32 words; compute: written here
+    uint64_t len;
+    uint64_t unit_begin;
+    uint64_t key_base;
+};
+
+// Units of a segment of len bytes at bpc <= 4096: its whole chunks cut into 4 KiB units, the
+// last one partial when the whole chunks end inside a round (PacketGeom); a short last chunk is
+// the kernel's one-lane tail
+constexpr uint64_t seg_units(uint64_t len, uint32_t bpc) { return (len / bpc * bpc + 4095) / 4096; }
+
+// Fills h_seg for n segments (data/crc/len/key_base already set) and returns the total
+// unit count (seg_units); *uniform = units per segment when every segment but the last has
+// the same count (direct unit -> segment mapping), else 0 (binary search).
+uint64_t plan_segments(DevSegment *h_seg, size_t n, uint32_t bpc, uint64_t *uniform);
+// True when the segmented wave kernel can take these segments: bpc in {512..4096},
+// every data pointer 16-byte aligned and every CRC pointer 4-byte aligned.
+bool segments_fast(const DevSegment *h_seg, size_t n, uint32_t bpc);
+
+// constant-pitch packet streams (ChunkLaunch::pitch): whether the wave kernel's pitch mode
+// takes them (bpc 512..4096 or R x 4096, aligned, every packet but the last whole chunks)
+bool packet_stream_ok(uint64_t data_len, uint64_t last_len, uint64_t npk, uint32_t bpc, const void *data,
+                      const void *crc, uint64_t pitch, PacketGeom *geom);
+
+// A packet stream the pitch walk takes (pitch_stream_launch, crc32c_kernels.h): crc_pitch 0 = pitch
+struct PitchStream {
+    uint64_t pitch = 0, crc_pitch = 0, npk = 0;
+    uint32_t last_len = 0;
+    PacketGeom geom;
+};
+// packet_stream_ok, and a piece scratch at bpc = R x 4096; lab variants 52 / 53 refuse every stream
+bool plan_packet_stream(uint64_t data_len, uint64_t last_len, uint64_t npk, uint32_t bpc, const void *data,
+                        const void *crc, uint64_t pitch, bool have_pieces, int variant, PitchStream *s);
+// equal blocks (the last may be shorter) whose data and words sit at two constant strides (blocks of one
+// 2-D tensor): the pitch mode with crc_pitch, at bpc <= 4096; false (lab variant 54): the segmented kernel
+bool plan_strided_blocks(const DevSegment *h_seg, size_t n, uint32_t bpc, int variant, PitchStream *s);
+
+enum class Route {
+    kPitchStream,      // one constant-pitch stream: the round kernel's pitch walk (plan.stream)
+    kStridedSegments,  // constant pitch, partial rounds: the segmented kernel derives every descriptor
+    kSegmentPieces,    // bpc = R x 4096 over a descriptor list: piece CRCs + the segments' combine
+    kInlineSegments,   // up to kInlineSegments descriptors in the kernel arguments
+    kMappedSegments,   // a long ragged list: descriptor array + the unit -> segment map
+    kStagedSegments,   // descriptor array copied to the device
+    kPackets,          // unaligned / other chunk sizes: the chunk-per-lane packet kernel
+    kOutOfBounds,      // packet bad_index lies outside [0, arena_len)
+};
+
+struct BatchPlan {
+    Route route = Route::kPackets;
+    PitchStream stream;    // kPitchStream; .pitch also kStridedSegments
+    uint64_t units = 0, uniform = 0;  // segment routes at bpc <= 4096: 4 KiB units; per segment when all agree
+    uint64_t pieces_total = 0, max_chunks = 0;  // kSegmentPieces: 4096-byte pieces; the most whole chunks in a segment
+    bool any_tail = false;    // kSegmentPieces: some segment ends in a short chunk
+    size_t bad_index = 0;     // kOutOfBounds
+};
+// Routes n >= 1 packets (offsets into an arena at device address `arena`) in one pass over h_pk with no
+// allocation (16K packets per GiB: on the call's critical path). arena_len != null: each packet is first
+// checked against [0, *arena_len). have_pieces: a PieceScratch is at hand. variant: the lab's knob (product:
+// 0); 17 forces kPackets, 52 descriptor arrays, 53 only refuses the pitch walk. h_stage[0..n) is filled for
+// the routes that read it: planned DevSegments (kSegmentPieces ... kStagedSegments), kPackets: the DevPackets.
+BatchPlan plan_packet_batch(uint64_t arena, const DevPacket *h_pk, size_t n, uint32_t bpc, const uint64_t *arena_len,
+                            bool have_pieces, int variant, DevSegment *h_stage);
+
+}  // namespace hdfs3crc
