@@ -301,6 +301,39 @@ int hdfs3_block_checksum_crcs(const void *crc_be, uint64_t n_crcs, uint8_t *md5_
 int hdfs3_file_checksum_md5md5crc(const uint8_t *block_md5s /* n_blocks x 16 B */, size_t n_blocks,
                                   uint8_t *md5_out /* 16 B */);
 
+/* ---- composite CRC (the CRC of a whole block or file, from chunk CRCs) --------
+ * The MD5-of-CRC digest above depends on bytesPerChecksum, and its file form on the block size:
+ * the same bytes chunked differently give different digests. The composite CRC is the CRC of
+ * the bytes themselves, derived from the stored chunk words without touching the data again:
+ * for finished CRCs, crc(A || B) = crc(A) * x^(8 |B|) ^ crc(B) in GF(2)[x] modulo the
+ * polynomial. It is independent of bpc and of the block size, which is what a block scanner, a
+ * replica compare or a copy check needs. Values are host-order uint32_t; the wire form (as for a
+ * stored word) is the value's 4 bytes big-endian. `type` is HDFS3_CHECKSUM_TYPE_CRC32C or _CRC32.
+ * All return 0 or -errno; -EINVAL for a type without a polynomial, bpc 0, a null buffer, and
+ * (n_crcs > 0) a last_len outside 1..bpc. The empty block and the empty file give 0.
+ *
+ * Host forms (no GPU context is created):
+ * hdfs3_crc_compose: the CRC of A || B from crc_a = crc(A), crc_b = crc(B) and len_b = |B|.
+ * hdfs3_block_composite_crc_crcs: from n_crcs big-endian words the caller holds (a .meta file's
+ *   body, any alignment), bpc bytes each but the last, which covers last_len bytes.
+ * hdfs3_file_checksum_composite_crc: from the blocks' composites and byte lengths, in block order. */
+int hdfs3_crc_compose(int type, uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t *crc_out);
+int hdfs3_block_composite_crc_crcs(int type, const void *crc_be, uint64_t n_crcs, uint32_t bpc, uint32_t last_len,
+                                   uint32_t *crc_out);
+int hdfs3_file_checksum_composite_crc(int type, const uint32_t *block_crcs, const uint64_t *block_lens,
+                                      size_t n_blocks, uint32_t *crc_out);
+/* Device forms, with the ctx's checksum type: a parallel reduction of the words on the GPU (a
+ * lane, wave, workgroup and grid tree; one more launch per 1024-fold), so only 4 bytes come back.
+ * _words_dev_async: words already in HBM (4-byte aligned, at most 2^40), as any compute call
+ *   writes them; launched on the ctx stream, nothing waits, the value lands in the caller-owned
+ *   device word *d_out (host order).
+ * _dev: computes the block's words into a scratch of the ctx (the compute launch of
+ *   hdfs3_crc32c_compute_dev), reduces them, and returns the value once it is ready. */
+int hdfs3_block_composite_crc_words_dev_async(hdfs3_crc_ctx *ctx, const void *d_crc_be, uint64_t n_crcs,
+                                              uint32_t bpc, uint32_t last_len, uint32_t *d_out);
+int hdfs3_block_composite_crc_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len, uint32_t bpc,
+                                  uint32_t *crc_out);
+
 /* ---- device memory helpers for FFI callers without a HIP binding ---------- */
 int hdfs3_dev_malloc(void **d_ptr, size_t bytes);
 int hdfs3_dev_free(void *d_ptr);

@@ -107,6 +107,13 @@ PUBLIC_API = {
     "hdfs3_block_checksum_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_uint32, c_void_p, POINTER(c_uint64)]),
     "hdfs3_block_checksum_crcs": (c_int, [c_void_p, c_uint64, c_void_p]),
     "hdfs3_file_checksum_md5md5crc": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "hdfs3_crc_compose": (c_int, [c_int, c_uint32, c_uint32, c_uint64, POINTER(c_uint32)]),
+    "hdfs3_block_composite_crc_crcs": (c_int, [c_int, c_void_p, c_uint64, c_uint32, c_uint32, POINTER(c_uint32)]),
+    "hdfs3_file_checksum_composite_crc": (c_int, [c_int, POINTER(c_uint32), POINTER(c_uint64), c_size_t,
+                                                  POINTER(c_uint32)]),
+    "hdfs3_block_composite_crc_words_dev_async": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_uint32,
+                                                          c_void_p]),
+    "hdfs3_block_composite_crc_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_uint32, POINTER(c_uint32)]),
     "hdfs3_multi_create": (c_int, [POINTER(c_int), c_int, POINTER(c_void_p)]),
     "hdfs3_multi_destroy": (None, [c_void_p]),
     "hdfs3_multi_device_count": (c_int, [c_void_p]),

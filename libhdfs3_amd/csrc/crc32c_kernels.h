@@ -152,6 +152,30 @@ hipError_t launch_packet_batch(const LaunchEnv &env, const uint8_t *d_arena, con
                                DevSegment *h_stage, DevSegment *d_stage, uint64_t arena_len = 0,
                                size_t *bad_index = nullptr, bool overlap_previous = false, bool *staged = nullptr);
 
+// Composite CRC of a block from its chunk words (crc32c_compose.hip). A lane runs Horner over
+// kComposeLaneWords consecutive words, a workgroup of kComposeThreads lanes reduces kComposeSpan words to
+// one partial, and the partials are reduced by the same kernel until one is left.
+constexpr int kComposeLaneWords = 4;
+constexpr int kComposeThreads = 256;
+constexpr uint64_t kComposeSpan = uint64_t(kComposeLaneWords) * kComposeThreads;
+constexpr uint64_t kComposeMaxWords = uint64_t(1) << 40;  // the first level's grid stays below 2^31
+// ctx-owned buffers of the composite calls, apart from the word and piece scratch of the compute paths:
+// the chunk words of a composite from data, and the workgroups' partials of every level
+struct ComposeScratch {
+    uint8_t *words = nullptr, *partials = nullptr;
+    uint64_t words_cap = 0, partials_cap = 0;
+    void release();
+};
+// Makes *d at least `need` bytes. The buffers serve launches of one stream at a time (a ctx's stream is
+// drained before it is switched), so a buffer that has to grow is freed after `stream` drained.
+hipError_t grow_compose_buffer(uint8_t **d, uint64_t *cap, uint64_t need, hipStream_t stream);
+// n >= 1 big-endian words at d_crc_be (4-byte aligned, n <= kComposeMaxWords), `unit` bytes each but the last
+// (`tail` bytes, 1..unit), polynomial `poly` -> the composite in *d_out (host order). Nothing waits;
+// *launched (if given) receives the number of kernel launches.
+hipError_t launch_compose_words(const LaunchEnv &env, ComposeScratch *scratch, const uint8_t *d_crc_be, uint64_t n,
+                                uint32_t unit, uint32_t tail, uint32_t poly, uint32_t *d_out,
+                                unsigned *launched = nullptr);
+
 // HDFS3_LAB=1 builds the measurement library (libhdfs3_crc_lab.so: tools/, the A/B tests):
 // the same production launchers plus a process-wide kernel-variant knob, the kernel
 // variants of crc32c_experiments.hip and the read-ceiling kernels. The product library

@@ -23,6 +23,7 @@
 #include "copy_pool.h"
 #include "crc32c_kernels.h"
 #include "crc32c_tables.h"
+#include "crc_compose.h"
 #include "ctx.h"
 #include "numa.h"
 
@@ -538,6 +539,7 @@ void hdfs3_crc_ctx_destroy(hdfs3_crc_ctx *ctx) {
     }
     ctx->words.release();
     ctx->pieces.release();
+    ctx->compose.release();
     for (int p = 0; p < 2; ++p) {
         if (ctx->d_tables_by[p]) (void)hipFree(ctx->d_tables_by[p]);
         if (ctx->d_fold_by[p]) (void)hipFree(ctx->d_fold_by[p]);
@@ -612,6 +614,7 @@ Footprint footprint(hdfs3_crc_ctx *ctx) {
     }
     f.pinned += sizeof(unsigned long long);
     f.device += ctx->words.cap + ctx->pieces.cap[0] + ctx->pieces.cap[1] + sizeof(unsigned long long);
+    f.device += ctx->compose.words_cap + ctx->compose.partials_cap;
     for (int p = 0; p < 2; ++p) f.device += sizeof(host_images()[p].t) + kFoldUploadBytes;
     return f;
 }
@@ -1055,6 +1058,114 @@ int hdfs3_file_checksum_md5md5crc(const uint8_t *block_md5s, size_t n_blocks, ui
     Md5 md5;
     md5.update(block_md5s, n_blocks * 16);
     md5.finish(md5_out);
+    return 0;
+}
+
+}  // extern "C"
+
+// Composite CRC (include/hdfs3_crc.h): the host forms are crc_compose.cpp's arithmetic, the device
+// forms reduce the words with crc32c_compose.hip.
+namespace {
+
+int poly_of_type(int type, uint32_t *poly) {
+    if (type != HDFS3_CHECKSUM_TYPE_CRC32C && type != HDFS3_CHECKSUM_TYPE_CRC32)
+        return fail(-EINVAL, "checksum type %d has no CRC polynomial", type);
+    *poly = type == HDFS3_CHECKSUM_TYPE_CRC32C ? kPolyReflected : kPolyCrc32;
+    return 0;
+}
+
+int check_words(uint64_t n_crcs, uint32_t bpc, uint32_t last_len) {
+    if (bpc == 0) return fail(-EINVAL, "bytes per checksum must be positive");
+    if (n_crcs && (last_len == 0 || last_len > bpc))
+        return fail(-EINVAL, "the last chunk holds %u bytes, not 1..%u", last_len, bpc);
+    return 0;
+}
+
+// the reduction of n >= 1 device words into *d_out on the ctx's stream
+int compose_words(hdfs3_crc_ctx *ctx, const void *d_crc_be, uint64_t n, uint32_t bpc, uint32_t last_len,
+                  uint32_t *d_out) {
+    if (n > kComposeMaxWords) return fail(-EINVAL, "%llu words in one composite", (unsigned long long)n);
+    if (reinterpret_cast<uintptr_t>(d_crc_be) & 3u) return fail(-EINVAL, "the words are not 4-byte aligned");
+    unsigned launched = 0;
+    const hipError_t e = launch_compose_words(launch_env(ctx), &ctx->compose, static_cast<const uint8_t *>(d_crc_be), n,
+                                              bpc, last_len, ctx->poly, d_out, &launched);
+    ctx->launches += launched;
+    HIP_TRY(e);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hdfs3_crc_compose(int type, uint32_t crc_a, uint32_t crc_b, uint64_t len_b, uint32_t *crc_out) {
+    uint32_t poly = 0;
+    if (int rc = poly_of_type(type, &poly)) return rc;
+    if (!crc_out) return fail(-EINVAL, "null out");
+    *crc_out = compose(crc_a, crc_b, len_b, poly);
+    return 0;
+}
+
+int hdfs3_block_composite_crc_crcs(int type, const void *crc_be, uint64_t n_crcs, uint32_t bpc, uint32_t last_len,
+                                   uint32_t *crc_out) {
+    uint32_t poly = 0;
+    if (int rc = poly_of_type(type, &poly)) return rc;
+    if (int rc = check_words(n_crcs, bpc, last_len)) return rc;
+    if (!crc_out || (n_crcs && !crc_be)) return fail(-EINVAL, "null buffer");
+    *crc_out = composite_of_words(crc_be, n_crcs, bpc, last_len, poly);
+    return 0;
+}
+
+int hdfs3_file_checksum_composite_crc(int type, const uint32_t *block_crcs, const uint64_t *block_lens,
+                                      size_t n_blocks, uint32_t *crc_out) {
+    uint32_t poly = 0;
+    if (int rc = poly_of_type(type, &poly)) return rc;
+    if (!crc_out || (n_blocks && (!block_crcs || !block_lens))) return fail(-EINVAL, "null buffer");
+    *crc_out = composite_of_blocks(block_crcs, block_lens, n_blocks, poly);
+    return 0;
+}
+
+int hdfs3_block_composite_crc_words_dev_async(hdfs3_crc_ctx *ctx, const void *d_crc_be, uint64_t n_crcs,
+                                              uint32_t bpc, uint32_t last_len, uint32_t *d_out) {
+    if (int rc = check_args(ctx, bpc)) return rc;
+    if (int rc = check_words(n_crcs, bpc, last_len)) return rc;
+    if (!d_out || (n_crcs && !d_crc_be)) return fail(-EINVAL, "null buffer");
+    DeviceGuard g(ctx->device);
+    if (n_crcs == 0) {  // the empty block
+        HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(uint32_t), ctx->stream));
+        return 0;
+    }
+    return compose_words(ctx, d_crc_be, n_crcs, bpc, last_len, d_out);
+}
+
+int hdfs3_block_composite_crc_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len, uint32_t bpc,
+                                  uint32_t *crc_out) {
+    if (int rc = check_args(ctx, bpc)) return rc;
+    if (!crc_out || (len && !d_data)) return fail(-EINVAL, "null buffer");
+    *crc_out = 0;
+    if (len == 0) return 0;
+    const uint64_t n = (uint64_t(len) + bpc - 1) / bpc;
+    if (n > kComposeMaxWords) return fail(-EINVAL, "%llu chunks in one composite", (unsigned long long)n);
+    DeviceGuard g(ctx->device);
+    ComposeScratch &cs = ctx->compose;
+    HIP_TRY(grow_compose_buffer(&cs.words, &cs.words_cap, n * 4, ctx->stream));
+    // the chunk words into the scratch, one compute launch per 4 Mi chunks as hdfs3_block_checksum_dev
+    for (uint64_t c0 = 0; c0 < n; c0 += kMd5PieceChunks) {
+        const uint64_t off = c0 * bpc;
+        ChunkLaunch a{};
+        a.data = static_cast<const uint8_t *>(d_data) + off;
+        a.len = std::min<uint64_t>(kMd5PieceChunks * bpc, uint64_t(len) - off);
+        a.bpc = bpc;
+        a.out_be = cs.words + 4 * c0;
+        if (int rc = launch(ctx, a, false)) return rc;
+    }
+    // the result word shares the verify calls' slot: a ctx serves one call at a time
+    uint32_t *d_out = reinterpret_cast<uint32_t *>(ctx->d_result);
+    const uint32_t last_len = uint32_t(uint64_t(len) - (n - 1) * bpc);
+    if (int rc = compose_words(ctx, cs.words, n, bpc, last_len, d_out)) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->h_result, d_out, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *crc_out = *reinterpret_cast<const uint32_t *>(ctx->h_result);
     return 0;
 }
 

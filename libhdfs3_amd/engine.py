@@ -212,6 +212,20 @@ class CrcContext:
               self._lib.hdfs3_block_checksum_dev(self.ctx, d_data, nbytes, bpc, _ptr(out), byref(n)))
         return out.tobytes(), n.value
 
+    # -- composite CRC (the block's own CRC, from its chunk words) ---------------------
+    def block_composite_crc_dev(self, d_data: int, nbytes: int, bpc: int) -> int:
+        """CRC of the resident block: chunk words and their reduction on the GPU, 4 bytes back."""
+        out = ctypes.c_uint32(0)
+        self._check("hdfs3_block_composite_crc_dev",
+              self._lib.hdfs3_block_composite_crc_dev(self.ctx, d_data, nbytes, bpc, byref(out)))
+        return out.value
+
+    def block_composite_crc_words_dev(self, d_crc: int, n_crcs: int, bpc: int, last_len: int, d_out: int) -> None:
+        """hdfs3_block_composite_crc_words_dev_async: resident BE words -> the device word d_out
+        (host order); nothing waits."""
+        self._check("hdfs3_block_composite_crc_words_dev_async",
+              self._lib.hdfs3_block_composite_crc_words_dev_async(self.ctx, d_crc, n_crcs, bpc, last_len, d_out))
+
     # -- packet-stream API ------------------------------------------------------------
     @staticmethod
     def _descs(pk) -> ctypes.Array:
@@ -289,6 +303,37 @@ def file_checksum_md5md5crc(block_md5s) -> bytes:
           _native.lib().hdfs3_file_checksum_md5md5crc(_ptr(buf) if buf.nbytes else None, buf.nbytes // 16,
                                                       _ptr(out)))
     return out.tobytes()
+
+
+def crc_compose(crc_a: int, crc_b: int, len_b: int, ctype: int = 2) -> int:
+    """hdfs3_crc_compose: CRC of A || B from crc(A), crc(B) and |B| (ctype 2 = CRC32C, 1 = CRC32)."""
+    out = ctypes.c_uint32(0)
+    check("hdfs3_crc_compose", _native.lib().hdfs3_crc_compose(ctype, crc_a, crc_b, len_b, byref(out)))
+    return out.value
+
+
+def block_composite_crc_crcs(crc_be: bytes | np.ndarray, bpc: int, last_len: int, ctype: int = 2) -> int:
+    """hdfs3_block_composite_crc_crcs: the block's CRC from its stored BE words (a .meta file's
+    body), bpc bytes each but the last (last_len bytes)."""
+    buf = np.frombuffer(bytes(crc_be), dtype=np.uint8)
+    out = ctypes.c_uint32(0)
+    check("hdfs3_block_composite_crc_crcs",
+          _native.lib().hdfs3_block_composite_crc_crcs(ctype, _ptr(buf) if buf.nbytes else None, buf.nbytes // 4,
+                                                       bpc, last_len, byref(out)))
+    return out.value
+
+
+def file_checksum_composite_crc(block_crcs, block_lens, ctype: int = 2) -> int:
+    """hdfs3_file_checksum_composite_crc: the file's CRC from its blocks' CRCs and lengths, in order."""
+    n = len(block_crcs)
+    assert len(block_lens) == n
+    crcs = (ctypes.c_uint32 * max(1, n))(*block_crcs)
+    lens = (ctypes.c_uint64 * max(1, n))(*block_lens)
+    out = ctypes.c_uint32(0)
+    check("hdfs3_file_checksum_composite_crc",
+          _native.lib().hdfs3_file_checksum_composite_crc(ctype, crcs if n else None, lens if n else None, n,
+                                                          byref(out)))
+    return out.value
 
 
 def block_checksum_remote(host: str, port: int, block_id: int, *, pool_id: bytes = b"BP-loopback",
