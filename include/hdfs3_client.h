@@ -60,6 +60,20 @@ int hdfs3_block_reader_open(const char *host, int port, const hdfs3_block_id *bl
 /* RemoteBlockReader::read (:332-357): copies up to len verified bytes; returns the
  * count (> 0), 0 once the range is exhausted, or -errno (-EIO on ChecksumException). */
 int32_t hdfs3_block_reader_read(hdfs3_block_reader *r, void *buf, int32_t len);
+/* hdfs3_block_reader_read into DEVICE memory: same counts, 0 at the end of the range, -EIO
+ * "ChecksumException" after the good packets before it, a short last chunk's mismatch ignored. d_buf
+ * is device memory of the reader's device (opts->device), e.g. a torch tensor's data_ptr(); a host
+ * pointer or another device's memory gives -EINVAL and leaves the reader usable. The verified bytes
+ * are already in HBM (the batch was uploaded for its verify), so they go from there to d_buf in one
+ * gather launch per batch (hdfs3_gather_dev_async's kernel) and no host copy-out is made. The launch
+ * is enqueued only after the host has read that batch's verify result, and only for the packets
+ * before a bad one: the reference's order, verify (RemoteBlockReader.cpp:253-255) before copy (:346).
+ * The returned bytes are in place when the call returns, and no byte of d_buf past the returned count
+ * is written. With verify = 0 or a CHECKSUM_NULL block the batch is uploaded for the delivery alone.
+ * read and read_dev may be mixed on one reader; each continues at the cursor. */
+int32_t hdfs3_block_reader_read_dev(hdfs3_block_reader *r, void *d_buf, int32_t len);
+/* gather launches made by read_dev so far and the bytes they placed */
+int hdfs3_block_reader_device_stats(hdfs3_block_reader *r, uint64_t *gather_launches, uint64_t *bytes_gathered);
 /* bytes already verified and buffered (BlockReader::available) */
 int64_t hdfs3_block_reader_available(hdfs3_block_reader *r);
 /* chunk size negotiated with the datanode, packets and GPU batches so far */
@@ -116,6 +130,16 @@ int32_t hdfs3_input_read(hdfs3_input_stream *s, void *buf, int32_t len);
 /* hdfsPread: reads [pos, pos+len) clipped to the file, across blocks; cursor unchanged.
  * pos outside the file returns -1 (preadInternal, InputStreamImpl.cpp:815-830). */
 int32_t hdfs3_input_pread(hdfs3_input_stream *s, int64_t pos, void *buf, int32_t len);
+/* hdfs3_input_read / hdfs3_input_pread with the destination in DEVICE memory (the stream's device,
+ * opts->device): the same block walk, replica failover, cursor rules and -1 + errno, every block read
+ * through hdfs3_block_reader_read_dev, so the verified bytes go from the batch in HBM to d_buf without a
+ * host copy. The bytes returned are in place when the call returns; nothing past them is written; after
+ * a failover the next replica's bytes continue at the same destination offset (pread_dev: from the
+ * range's first byte, as pread). When every replica fails (-1, EIO), whatever the destination holds
+ * beyond the count is either verified file data or what it held before. A pointer that is not memory of
+ * the stream's device gives -1 / EINVAL and burns no replica. Both may be mixed with the host calls. */
+int32_t hdfs3_input_read_dev(hdfs3_input_stream *s, void *d_buf, int32_t len);
+int32_t hdfs3_input_pread_dev(hdfs3_input_stream *s, int64_t pos, void *d_buf, int32_t len);
 /* hdfsSeek: a forward seek of <= 128 KiB inside the current block skips through the open
  * reader (InputStreamImpl.cpp:1146-1152); anything else reopens at the target. */
 int hdfs3_input_seek(hdfs3_input_stream *s, int64_t pos);

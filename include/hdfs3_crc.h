@@ -278,6 +278,41 @@ int hdfs3_crc32c_verify_packet_stream_dev_async(hdfs3_crc_ctx *ctx, const void *
 int hdfs3_crc32c_compute_packet_stream_dev_async(hdfs3_crc_ctx *ctx, void *d_arena, size_t arena_len,
                                                  const hdfs3_pkt_stream *ps, uint32_t bpc);
 
+/* ---- range gather: verified bytes delivered inside device memory -----------------
+ * A reader's verified batch sits in HBM as packets ([words][data] each, or all words then all data);
+ * a consumer on the GPU wants the data alone, back to back, in a buffer of its own. One launch of the
+ * gather kernel copies n byte ranges from one device buffer to another: any offsets and lengths (0
+ * included), no alignment asked of either side, only the bytes [dst_off, dst_off + len) of each range
+ * written (partial 16-byte lines at a range's ends are written byte by byte, never read back and
+ * merged), the work split by bytes so one long range and many short ones both fill the device. Up to 64
+ * ranges travel in one launch's kernel arguments; longer lists take more launches. Empty ranges are
+ * dropped, and a range that continues its predecessor in both buffers is copied as part of it.
+ *
+ * hdfs3_gather_dev_async: n ranges from d_src to d_dst in one pass on the ctx stream; nothing waits.
+ * ranges[] is host memory, consumed before return. -EINVAL (before any launch) for a null ctx, a null
+ * pointer with n > 0, or a range outside src_len / dst_len. Destination ranges must not overlap each
+ * other or the source (not checked). Unlike the verify and compute calls it uses none of the ctx's
+ * staging, so a thread other than the ctx's own may call it while that one works (the block reader's
+ * caller thread does); its launches count in hdfs3_crc_ctx_kernel_launches. */
+typedef struct hdfs3_copy_range {
+    uint64_t src_off; /* first byte in d_src */
+    uint64_t dst_off; /* first byte in d_dst */
+    uint64_t len;     /* bytes               */
+} hdfs3_copy_range;
+int hdfs3_gather_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len,
+                           const hdfs3_copy_range *ranges, size_t n);
+/* Verify-then-deliver for callers with their own transport: verifies the packets exactly as
+ * hdfs3_crc32c_verify_packets_dev (same bad_packet / bad_chunk), reads the result, and only then
+ * gathers the data of every packet BEFORE the first bad one, back to back, to d_dst + dst_off (all
+ * packets when clean). Nothing of the bad packet or any later one is written: the reference's order,
+ * verify (RemoteBlockReader.cpp:253-255) before copy (:346). *delivered = bytes placed, complete when
+ * the call returns. -EINVAL (nothing verified or written) if all n packets' data cannot fit in
+ * dst_len behind dst_off, or d_dst is null while they hold any data. */
+int hdfs3_crc32c_verify_packets_gather_dev(hdfs3_crc_ctx *ctx, const void *d_arena, size_t arena_len,
+                                           const hdfs3_pkt_desc *pk, size_t n, uint32_t bpc, int check_short_tail,
+                                           void *d_dst, size_t dst_len, uint64_t dst_off,
+                                           int64_t *bad_packet, int64_t *bad_chunk, uint64_t *delivered);
+
 /* ---- streaming shim ---------------------------------------------------------
  * Checksum::update on a raw state (seed 0xFFFFFFFF = reset(), ~state = getValue()),
  * for sub-chunk pieces only: the partial chunk a writer carries across append()

@@ -107,6 +107,13 @@ int hdfs3_fs_set_append_stamp(hdfsFS fs, const char *path, uint64_t new_generati
  * hdfs3_client.h; 0 blocks = off, the reference's one-block-at-a-time reading; at most
  * HDFS3_READAHEAD_MAX_BLOCKS). 0, or -1 with errno (EINVAL). */
 int hdfs3_fs_set_readahead(hdfsFS fs, int blocks, int64_t max_bytes_per_block);
+/* hdfsRead / hdfsPread with the destination in DEVICE memory (hdfs3_input_read_dev / _pread_dev in
+ * hdfs3_client.h): d_buffer is memory of the GPU the fs's read_opts name, e.g. a torch tensor's
+ * data_ptr(). Same counts, cursor rules, failover and -1 + errno as hdfsRead / hdfsPread; the bytes
+ * returned are verified and in place when the call returns, nothing past them is written, and no host
+ * copy of them is made. Both kinds of read may be mixed on one hdfsFile. */
+tSize hdfs3_fs_read_dev(hdfsFS fs, hdfsFile file, void *d_buffer, tSize length);
+tSize hdfs3_fs_pread_dev(hdfsFS fs, hdfsFile file, void *d_buffer, tSize length, tOffset position);
 
 #ifdef __cplusplus
 }

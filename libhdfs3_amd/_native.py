@@ -44,6 +44,12 @@ class DevBlock(ctypes.Structure):
     _fields_ = [("data", c_void_p), ("crc_be", c_void_p), ("len", c_uint64)]
 
 
+class CopyRange(ctypes.Structure):
+    """hdfs3_copy_range (include/hdfs3_crc.h)."""
+
+    _fields_ = [("src_off", c_uint64), ("dst_off", c_uint64), ("len", c_uint64)]
+
+
 # name -> (restype, argtypes); every symbol include/hdfs3_crc.h declares.
 PUBLIC_API = {
     "hdfs3_crc_abi_version": (c_int, []),
@@ -88,6 +94,10 @@ PUBLIC_API = {
                                                             c_uint32, c_int, c_void_p, c_uint32]),
     "hdfs3_crc32c_compute_packet_stream_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(PktStream),
                                                              c_uint32]),
+    "hdfs3_gather_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(CopyRange), c_size_t]),
+    "hdfs3_crc32c_verify_packets_gather_dev": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(PktDesc), c_size_t,
+                                                       c_uint32, c_int, c_void_p, c_size_t, c_uint64,
+                                                       POINTER(c_int64), POINTER(c_int64), POINTER(c_uint64)]),
     "hdfs3_crc32c_update_host": (c_uint32, [c_uint32, c_void_p, c_size_t]),
     "hdfs3_dev_malloc": (c_int, [POINTER(c_void_p), c_size_t]),
     "hdfs3_dev_free": (c_int, [c_void_p]),
@@ -209,6 +219,8 @@ CLIENT_API = {
     "hdfs3_block_reader_open": (c_int, [ctypes.c_char_p, c_int, POINTER(BlockId), c_int64, c_int64,
                                         ctypes.c_char_p, POINTER(ReaderOpts), POINTER(c_void_p)]),
     "hdfs3_block_reader_read": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_block_reader_read_dev": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_block_reader_device_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "hdfs3_block_reader_available": (c_int64, [c_void_p]),
     "hdfs3_block_reader_stats": (c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint64), POINTER(c_uint64)]),
     "hdfs3_reader_phase_ns": (c_int, [POINTER(c_uint64), c_int, c_int]),
@@ -217,6 +229,8 @@ CLIENT_API = {
                                  POINTER(c_void_p)]),
     "hdfs3_input_read": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
     "hdfs3_input_pread": (ctypes.c_int32, [c_void_p, c_int64, c_void_p, ctypes.c_int32]),
+    "hdfs3_input_read_dev": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_input_pread_dev": (ctypes.c_int32, [c_void_p, c_int64, c_void_p, ctypes.c_int32]),
     "hdfs3_input_seek": (c_int, [c_void_p, c_int64]),
     "hdfs3_input_tell": (c_int64, [c_void_p]),
     "hdfs3_input_available": (c_int, [c_void_p]),
@@ -279,6 +293,8 @@ HDFS_API = {
     "hdfs3_fs_set_sink": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_void_p]),
     "hdfs3_fs_set_pipeline": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_int]),
     "hdfs3_fs_set_readahead": (c_int, [c_void_p, c_int, c_int64]),
+    "hdfs3_fs_read_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_fs_pread_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32, c_int64]),
     "hdfs3_fs_set_append_stamp": (c_int, [c_void_p, ctypes.c_char_p, c_uint64]),
     "hdfs3_fs_set_block_size": (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_int64]),
 }

@@ -9,6 +9,8 @@
 //   GPU              verifies batch i while the receiver fills batch i+1
 //   caller (read)    waits for the front batch's event, copies its verified bytes out,
 //                    returns the arena to the receiver
+//   caller (read_dev) the same, but the verified bytes go from the arena's device copy to the
+//                    caller's device buffer in one gather launch per batch (no host copy-out)
 // so socket receive, verification and delivery overlap; the reference does all three in
 // sequence on the caller's thread (RemoteBlockReader::read, :332-357). Delivery only ever
 // comes from a batch whose verification completed.
@@ -85,6 +87,7 @@ struct Batch {
     bool dense = false, sealed = false;
     uint64_t d0 = 0, words_used = 0, data_used = 0;
     std::vector<uint64_t> chunk0;
+    bool uploaded = false;  // the arena's device copy holds the batch (launch(), or read_dev for an unverified one)
 
     void reset() {
         used = 0;
@@ -95,6 +98,7 @@ struct Batch {
         dense = sealed = false;
         d0 = words_used = data_used = 0;
         chunk0.clear();
+        uploaded = false;
     }
 };
 
@@ -221,6 +225,8 @@ struct hdfs3_block_reader {
     std::string error_msg;
 
     std::atomic<uint64_t> packets{0}, batches{0};
+    std::atomic<uint64_t> dev_launches{0}, dev_bytes{0};  // read_dev: gather launches, bytes they placed
+    hipEvent_t dev_done = nullptr;                        // read_dev: recorded after a call's last gather
     // receive, alloc, launch, wait, deliver (hdfs3x_block_reader_timing), then (round 6) the receiver's
     // waits for a free slot, the caller's waits for a ready batch, the receiver thread's CPU time:
     // summed into g_phase_ns when the reader closes (hdfs3_reader_phase_ns)
@@ -441,6 +447,7 @@ struct hdfs3_block_reader {
         env.tables = tables;
         env.fold = ctx->d_fold_by[tables == ctx->d_tables_by[1]];
         HIP_OK(hipMemcpyAsync(b.a.d, b.a.h, b.used, hipMemcpyHostToDevice, ctx->stream));
+        b.uploaded = true;
         HIP_OK(hipMemsetAsync(b.a.d_res, 0, sizeof(unsigned long long), ctx->stream));
         if (b.dense) {
             // one contiguous block of b.data_used bytes and its word array: the contiguous round kernel
@@ -537,19 +544,24 @@ struct hdfs3_block_reader {
     }
 
     // ---- caller side ----------------------------------------------------------------------
-    int wait(Batch &b) {
-        if (b.verified) return 0;
+    int wait_event(hipEvent_t ev) {
         Timer tm(t_ns[3]);
         if (wait_mode == kWaitBlock) {
-            HIP_OK(hipEventSynchronize(b.a.done));  // a blocking-sync event (grow())
+            HIP_OK(hipEventSynchronize(ev));  // a blocking-sync event (grow())
         } else {
             for (;;) {
-                const hipError_t q = hipEventQuery(b.a.done);
+                const hipError_t q = hipEventQuery(ev);
                 if (q == hipSuccess) break;
                 if (q != hipErrorNotReady) HIP_OK(q);
                 if (wait_mode == kWaitPoll) std::this_thread::sleep_for(std::chrono::microseconds(kWaitPollUs));
             }
         }
+        return 0;
+    }
+
+    int wait(Batch &b) {
+        if (b.verified) return 0;
+        if (int rc = wait_event(b.a.done)) return rc;
         const unsigned long long r = *b.a.h_res;
         if (r && b.dense) {  // the first bad chunk of the batch -> its packet
             const uint64_t chunk = ~r;
@@ -649,6 +661,128 @@ struct hdfs3_block_reader {
         return total;
     }
 
+    // read() into device memory: the same loop, but a verified batch's bytes go from the arena's DEVICE copy
+    // (uploaded for the verify) to d_out in one gather launch per batch, on the ctx stream, enqueued only
+    // after wait() has read the batch's verify result and only for the packets before bad_pkt. The
+    // caller's thread launches on the stream the receiver launches on; it touches none of the ctx's
+    // descriptor rings or scratch (gather_dev: ranges in the kernel arguments).
+    int32_t read_dev(uint8_t *d_out, int32_t len) {
+        if (error) return fail(error, "%s", error_msg.c_str());
+        if (len <= 0 || !d_out) return fail(-EINVAL, "invalid read buffer");
+        DeviceGuard guard(ctx->device);
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, d_out) != hipSuccess || at.type != hipMemoryTypeDevice ||
+            at.device != ctx->device) {
+            (void)hipGetLastError();  // a host pointer is the caller's mistake, not a fault of the GPU
+            return fail(-EINVAL, "read_dev: the buffer is not device memory of device %d", ctx->device);
+        }
+        if (!dev_done) HIP_OK(hipEventCreateWithFlags(&dev_done, hipEventDisableTiming | hipEventBlockingSync));
+        int32_t total = 0;
+        int failed = 0;         // the call ends with this error once its gathers completed
+        bool enqueued = false;  // gathers not yet known complete
+        std::vector<CopyRange> rg;
+        auto complete = [&]() -> int {  // an event after the last gather, waited for
+            if (!enqueued) return 0;
+            HIP_OK(hipEventRecord(dev_done, ctx->stream));
+            if (int rc = wait_event(dev_done)) return rc;
+            enqueued = false;
+            return 0;
+        };
+        while (total < len && !failed) {
+            int s;
+            {
+                Timer idle(t_ns[6]);
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return !ready.empty() || recv_done; });
+                if (ready.empty()) {
+                    if (recv_error) {  // good batches were all delivered first
+                        error = recv_error;
+                        error_msg = recv_msg;
+                        failed = error;
+                    }
+                    break;  // range exhausted
+                }
+                s = ready.front();
+            }
+            Batch &b = slot[s];
+            if (int rc = wait(b)) {
+                local_fault = true;
+                error = failed = rc;
+                error_msg = hdfs3_crc_last_error();
+                break;
+            }
+            const size_t limit = b.bad_pkt >= 0 ? size_t(b.bad_pkt) : b.pk.size();
+            {
+                Timer tm(t_ns[4]);
+                rg.clear();
+                const int32_t before = total;
+                while (total < len && b.dpkt < limit) {
+                    const PacketRef &p = b.pk[b.dpkt];
+                    const size_t n = std::min<size_t>(p.deliver - b.doff, size_t(len - total));
+                    rg.push_back(CopyRange{p.data_off + p.skip + b.doff, uint64_t(total), n});
+                    total += int32_t(n);
+                    b.doff += n;
+                    delivered += int64_t(n);
+                    if (b.doff == p.deliver) {
+                        ++b.dpkt;
+                        b.doff = 0;
+                    }
+                }
+                int rc = 0;
+                if (total > before) {
+                    // verify off or a CHECKSUM_NULL block: launch() uploaded nothing, so this thread does.
+                    // The receiver refills the HOST arena once the slot is free, which no stream orders
+                    // against the upload: such a batch's copies are waited for before it goes back.
+                    const bool own_upload = !b.uploaded;
+                    if (own_upload) {
+                        const hipError_t e = hipMemcpyAsync(b.a.d, b.a.h, b.used, hipMemcpyHostToDevice, ctx->stream);
+                        if (e != hipSuccess) rc = hip_err(e, "hipMemcpyAsync");
+                        b.uploaded = true;
+                    }
+                    unsigned launched = 0;
+                    if (!rc) rc = gather_dev(ctx, d_out, size_t(len), b.a.d, b.used, rg.data(), rg.size(), &launched);
+                    enqueued = true;
+                    if (!rc && own_upload) rc = complete();
+                    dev_launches.fetch_add(launched, std::memory_order_relaxed);
+                    dev_bytes.fetch_add(uint64_t(total - before), std::memory_order_relaxed);
+                }
+                if (rc) {
+                    local_fault = true;
+                    error = failed = rc;
+                    error_msg = hdfs3_crc_last_error();
+                    break;
+                }
+            }
+            if (b.dpkt == limit) {
+                if (b.bad_pkt >= 0) {
+                    failed = sticky(-EIO, "ChecksumException: RemoteBlockReader: checksum not match for Block: " +
+                                              std::to_string(block.block_id) + " (packet " + std::to_string(b.bad_pkt) +
+                                              " of a GPU batch)");
+                    break;
+                }
+                // the batch's gather is in the stream that carries this arena's next upload, which is
+                // thereby ordered behind it: the slot can go back now
+                {
+                    std::lock_guard<std::mutex> lk(mu);
+                    ready.pop_front();
+                    free_slots.push_back(s);
+                }
+                cv.notify_all();
+            }
+        }
+        // the returned bytes are in place when the call returns: an event after the last gather, not a
+        // drain of the stream (the receiver may have queued the next batch's upload and verify behind it)
+        if (int rc = complete()) {
+            local_fault = true;
+            error = failed = rc;
+            error_msg = hdfs3_crc_last_error();
+            total = 0;  // nothing is known to be in place
+        }
+        if (failed) return total ? total : fail(error, "%s", error_msg.c_str());
+        maybe_send_status();
+        return total;
+    }
+
     int64_t available() {
         std::lock_guard<std::mutex> lk(mu);
         int64_t a = 0;
@@ -672,6 +806,7 @@ struct hdfs3_block_reader {
             rx.join();
         }
         if (ctx) (void)hipStreamSynchronize(ctx->stream);
+        if (dev_done) (void)hipEventDestroy(dev_done);
         for (int i = 0; i < kPhases; ++i) g_phase_ns[i].fetch_add(t_ns[i].load(), std::memory_order_relaxed);
         // a borrowed ctx keeps up to a ring's worth of arenas for its next reader (a read-ahead
         // reader's deep ring included: the stream's next read-ahead takes them back)
@@ -799,6 +934,18 @@ int hdfs3_block_reader_open(const char *host, int port, const hdfs3_block_id *bl
 int32_t hdfs3_block_reader_read(hdfs3_block_reader *r, void *buf, int32_t len) {
     if (!r) return fail(-EINVAL, "null reader");
     return r->read(static_cast<uint8_t *>(buf), len);
+}
+
+int32_t hdfs3_block_reader_read_dev(hdfs3_block_reader *r, void *d_buf, int32_t len) {
+    if (!r) return fail(-EINVAL, "null reader");
+    return r->read_dev(static_cast<uint8_t *>(d_buf), len);
+}
+
+int hdfs3_block_reader_device_stats(hdfs3_block_reader *r, uint64_t *gather_launches, uint64_t *bytes_gathered) {
+    if (!r) return fail(-EINVAL, "null reader");
+    if (gather_launches) *gather_launches = r->dev_launches.load();
+    if (bytes_gathered) *bytes_gathered = r->dev_bytes.load();
+    return 0;
 }
 
 int64_t hdfs3_block_reader_available(hdfs3_block_reader *r) { return r ? r->available() : 0; }

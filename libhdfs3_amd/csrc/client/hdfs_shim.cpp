@@ -448,6 +448,23 @@ tSize hdfsPread(hdfsFS fs, hdfsFile file, void *buffer, tSize length, tOffset po
     return n;
 }
 
+// hdfsRead / hdfsPread into device memory (not in hdfs.h): same checks, returns and errno
+tSize hdfs3_fs_read_dev(hdfsFS fs, hdfsFile file, void *d_buffer, tSize length) {
+    PARAMETER_ASSERT(fs && file && d_buffer && length > 0, -1, EINVAL);
+    PARAMETER_ASSERT(file->input, -1, EINVAL);
+    const int32_t n = hdfs3_input_read_dev(file->in, d_buffer, length);
+    if (n < 0) return stream_failed(tSize(-1));
+    return n;
+}
+
+tSize hdfs3_fs_pread_dev(hdfsFS fs, hdfsFile file, void *d_buffer, tSize length, tOffset position) {
+    PARAMETER_ASSERT(fs && file && d_buffer && length > 0 && position >= 0, -1, EINVAL);
+    PARAMETER_ASSERT(file->input, -1, EINVAL);
+    const int32_t n = hdfs3_input_pread_dev(file->in, position, d_buffer, length);
+    if (n < 0) return stream_failed(tSize(-1));
+    return n;
+}
+
 tSize hdfsWrite(hdfsFS fs, hdfsFile file, const void *buffer, tSize length) {
     PARAMETER_ASSERT(fs && file && buffer && length > 0, -1, EINVAL);
     PARAMETER_ASSERT(!file->input, -1, EINVAL);

@@ -212,8 +212,13 @@ struct hdfs3_input_stream {
         else if (!ahead.empty()) drop_ahead(i);
     }
 
-    // readOneBlock (:616-712)
-    int32_t read_one_block(uint8_t *buf, int32_t size) {
+    // the block reader's read into host memory, or (dev) into device memory
+    static int32_t reader_read(hdfs3_block_reader *r, uint8_t *buf, int32_t size, bool dev) {
+        return dev ? hdfs3_block_reader_read_dev(r, buf, size) : hdfs3_block_reader_read(r, buf, size);
+    }
+
+    // readOneBlock (:616-712); dev: buf is device memory (hdfs3_block_reader_read_dev)
+    int32_t read_one_block(uint8_t *buf, int32_t size, bool dev) {
         const Block &b = blocks[cur];
         for (;;) {
             if (!reader) {
@@ -221,9 +226,14 @@ struct hdfs3_input_stream {
                 if (int rc = setup(b, off, b.length - off, &reader, &cur_node)) return rc;
             }
             const int32_t todo = int32_t(std::min<int64_t>(size, end_of_cur_block - cursor));
-            const int32_t n = hdfs3_block_reader_read(reader, buf, todo);
+            const int32_t n = reader_read(reader, buf, todo, dev);
             if (n > 0) {
                 cursor += n;
+                return n;
+            }
+            // a destination that is not this device's memory is the caller's mistake, not the replica's
+            if (dev && n == -EINVAL) {
+                last_error = hdfs3_crc_last_error();
                 return n;
             }
             // a local GPU/memory fault is not the replica's: report it, do not burn the replicas.
@@ -248,18 +258,20 @@ struct hdfs3_input_stream {
         }
     }
 
-    int32_t read(uint8_t *buf, int32_t size) {
+    int32_t read(uint8_t *buf, int32_t size, bool dev = false) {
         if (cursor >= file_length) return 0;  // HdfsEndOfStream -> hdfsRead returns 0
         if (cursor >= end_of_cur_block || cur < 0) {
             const int i = find_block(cursor);
             if (i < 0) return -EIO;
             seek_to_block(i);
         }
-        return read_one_block(buf, size);
+        return read_one_block(buf, size, dev);
     }
 
     // fetchBlockByteRange (:955-1061): the whole range from one replica, else the next
-    int fetch_range(const Block &b, int64_t start, int64_t len, uint8_t *out) {
+    // dev: `out` is device memory: no eager destination goes to the reader (its receiver would memcpy
+    // into a device pointer), and a replica that fails is read again from `out` on, as on the host
+    int fetch_range(const Block &b, int64_t start, int64_t len, uint8_t *out, bool dev) {
         std::vector<Node> saved;
         saved.swap(failed);
         int rc = 0;
@@ -271,12 +283,12 @@ struct hdfs3_input_stream {
             // loop's, rate within the spread, profiles/r06/r6eg_config5_eager_ab.jsonl).
             // HDFS3_READER_EAGER_COPY=0 (measurement knob) leaves the copy to read()
             const char *ev = getenv("HDFS3_READER_EAGER_COPY");
-            const bool eager = !(ev && ev[0] == '0');
+            const bool eager = !dev && !(ev && ev[0] == '0');
             if ((rc = setup(b, start, len, &r, &node, eager ? out : nullptr))) break;
             int64_t got = 0;
             int32_t n = 0;
             while (got < len) {
-                n = hdfs3_block_reader_read(r, out + got, int32_t(std::min<int64_t>(len - got, 1 << 30)));
+                n = reader_read(r, out + got, int32_t(std::min<int64_t>(len - got, 1 << 30)), dev);
                 if (n <= 0) break;
                 got += n;
             }
@@ -284,7 +296,8 @@ struct hdfs3_input_stream {
             if (local) last_error = hdfs3_crc_last_error();
             hdfs3_block_reader_close(r);
             if (got == len) break;
-            if (local) {  // this host's GPU, not the replica: no failover
+            if (local || (dev && n == -EINVAL)) {  // this host's GPU or the caller's pointer, not the replica: no failover
+                if (!local) last_error = hdfs3_crc_last_error();
                 rc = n < 0 ? n : -EIO;
                 break;
             }
@@ -295,7 +308,7 @@ struct hdfs3_input_stream {
         return rc;
     }
 
-    int32_t pread(int64_t pos, uint8_t *buf, int32_t size) {
+    int32_t pread(int64_t pos, uint8_t *buf, int32_t size, bool dev = false) {
         if (pos < 0 || pos >= file_length) return -EINVAL;
         const int32_t real = int32_t(std::min<int64_t>(size, file_length - pos));
         int64_t done = 0;
@@ -305,7 +318,7 @@ struct hdfs3_input_stream {
             const Block &b = blocks[i];
             const int64_t start = pos + done - b.offset;
             const int64_t n = std::min<int64_t>(real - done, b.length - start);
-            if (int rc = fetch_range(b, start, n, buf + done)) return rc;
+            if (int rc = fetch_range(b, start, n, buf + done, dev)) return rc;
             done += n;
         }
         return real;
@@ -394,6 +407,23 @@ int32_t hdfs3_input_pread(hdfs3_input_stream *s, int64_t pos, void *buf, int32_t
     s->last_error.clear();
     const int32_t rc = s->pread(pos, static_cast<uint8_t *>(buf), len);
     if (rc == -EINVAL) return posix_fail(EINVAL, "hdfsPread: position outside the file");
+    if (rc < 0) return posix_fail(-rc, s->last_error.empty() ? hdfs3_crc_last_error() : s->last_error);
+    return rc;
+}
+
+int32_t hdfs3_input_read_dev(hdfs3_input_stream *s, void *d_buf, int32_t len) {
+    if (!s || !d_buf || len <= 0) return posix_fail(EINVAL, "hdfs3_input_read_dev: invalid argument");
+    s->last_error.clear();
+    const int32_t rc = s->read(static_cast<uint8_t *>(d_buf), len, true);
+    if (rc < 0) return posix_fail(-rc, s->last_error.empty() ? hdfs3_crc_last_error() : s->last_error);
+    return rc;
+}
+
+int32_t hdfs3_input_pread_dev(hdfs3_input_stream *s, int64_t pos, void *d_buf, int32_t len) {
+    if (!s || !d_buf || len <= 0 || pos < 0) return posix_fail(EINVAL, "hdfs3_input_pread_dev: invalid argument");
+    if (pos >= s->file_length) return posix_fail(EINVAL, "hdfs3_input_pread_dev: position outside the file");
+    s->last_error.clear();
+    const int32_t rc = s->pread(pos, static_cast<uint8_t *>(d_buf), len, true);
     if (rc < 0) return posix_fail(-rc, s->last_error.empty() ? hdfs3_crc_last_error() : s->last_error);
     return rc;
 }

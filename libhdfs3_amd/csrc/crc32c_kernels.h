@@ -176,6 +176,12 @@ hipError_t launch_compose_words(const LaunchEnv &env, ComposeScratch *scratch, c
                                 uint32_t unit, uint32_t tail, uint32_t poly, uint32_t *d_out,
                                 unsigned *launched = nullptr);
 
+// One planned gather launch (crc32c_gather.hip; plan_gather_launch, launch_plan.h): g's ranges from d_src to
+// d_dst, its descriptors in the kernel arguments, so nothing of g is read after the call returns and no
+// staging buffer is involved (any thread may launch on `stream`). g.n == 0 launches nothing.
+hipError_t launch_gather(hipStream_t stream, void *d_dst, uint64_t dst_len, const void *d_src, uint64_t src_len,
+                         const GatherLaunch &g);
+
 // HDFS3_LAB=1 builds the measurement library (libhdfs3_crc_lab.so: tools/, the A/B tests):
 // the same production launchers plus a process-wide kernel-variant knob, the kernel
 // variants of crc32c_experiments.hip and the read-ceiling kernels. The product library

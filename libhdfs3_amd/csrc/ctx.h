@@ -148,5 +148,11 @@ inline LaunchEnv launch_env(hdfs3_crc_ctx *ctx, PieceScratch *own_pieces = nullp
     return LaunchEnv{ctx->d_tables, ctx->d_fold, ctx->grid_cap, ctx->stream, own_pieces ? nullptr : &ctx->words,
                      own_pieces ? own_pieces : &ctx->pieces, nullptr};
 }
+// hdfs3_gather_dev_async without its argument checks: every range checked first (-EINVAL before any launch),
+// then one gather launch per kGatherMaxRanges planned ranges on the ctx stream. Touches the ctx's stream and
+// launch counter only, so the block reader's caller thread may run it beside the receiver's launches (the
+// calling thread's current device is the ctx's). *launched (if given) is raised by the launches made.
+int gather_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len, const CopyRange *r,
+               size_t n, unsigned *launched = nullptr);
 }  // namespace hdfs3crc
 

@@ -742,6 +742,25 @@ void ctx_release(hdfs3_crc_ctx *ctx) {
 
 }  // namespace hdfs3crc
 
+namespace hdfs3crc {
+int gather_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len, const CopyRange *r,
+               size_t n, unsigned *launched) {
+    const size_t bad = gather_first_bad(r, n, src_len, dst_len);
+    if (bad != n)
+        return fail(-EINVAL, "range %zu lies outside the %zu-byte source or the %zu-byte destination", bad, src_len,
+                    dst_len);
+    GatherLaunch g;
+    for (size_t pos = 0; pos < n;) {
+        pos = plan_gather_launch(reinterpret_cast<uintptr_t>(d_dst), r, n, pos, &g);
+        if (g.n == 0) continue;  // nothing but empty ranges
+        HIP_TRY(launch_gather(ctx->stream, d_dst, dst_len, d_src, src_len, g));
+        ++ctx->launches;
+        if (launched) ++*launched;
+    }
+    return 0;
+}
+}  // namespace hdfs3crc
+
 extern "C" {
 
 int hdfs3_crc_ctx_acquire(int device, hdfs3_crc_ctx **out) { return hdfs3crc::ctx_acquire(device, out); }
@@ -964,6 +983,59 @@ int hdfs3_crc32c_compute_packets_dev_async(hdfs3_crc_ctx *ctx, void *d_arena, si
     if (!d_arena || !pk) return fail(-EINVAL, "null buffer");
     DeviceGuard g(ctx->device);
     return packets_async(ctx, static_cast<const uint8_t *>(d_arena), arena_len, pk, n, bpc, false, 0, nullptr, false);
+}
+
+static_assert(sizeof(hdfs3_copy_range) == sizeof(CopyRange) && offsetof(hdfs3_copy_range, src_off) == offsetof(CopyRange, src_off) &&
+                  offsetof(hdfs3_copy_range, dst_off) == offsetof(CopyRange, dst_off) &&
+                  offsetof(hdfs3_copy_range, len) == offsetof(CopyRange, len),
+              "the gather hands its ranges to the planner unconverted");
+
+int hdfs3_gather_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len,
+                           const hdfs3_copy_range *ranges, size_t n) {
+    if (!ctx) return fail(-EINVAL, "null hdfs3_crc_ctx");
+    if (n == 0) return 0;
+    if (!d_dst || !d_src || !ranges) return fail(-EINVAL, "null buffer");
+    DeviceGuard g(ctx->device);
+    return gather_dev(ctx, d_dst, dst_len, d_src, src_len, reinterpret_cast<const CopyRange *>(ranges), n);
+}
+
+int hdfs3_crc32c_verify_packets_gather_dev(hdfs3_crc_ctx *ctx, const void *d_arena, size_t arena_len,
+                                           const hdfs3_pkt_desc *pk, size_t n, uint32_t bpc, int check_short_tail,
+                                           void *d_dst, size_t dst_len, uint64_t dst_off,
+                                           int64_t *bad_packet, int64_t *bad_chunk, uint64_t *delivered) {
+    if (int rc = check_args(ctx, bpc)) return rc;
+    if (bad_packet) *bad_packet = -1;
+    if (bad_chunk) *bad_chunk = -1;
+    if (delivered) *delivered = 0;
+    if (n == 0) return 0;
+    if (!d_arena || !pk) return fail(-EINVAL, "null buffer");
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) total += pk[i].data_len;
+    if (dst_off > dst_len || total > dst_len - dst_off)
+        return fail(-EINVAL, "%llu bytes of packet data do not fit the %zu-byte destination at offset %llu",
+                    (unsigned long long)total, dst_len, (unsigned long long)dst_off);
+    if (total && !d_dst) return fail(-EINVAL, "null buffer");
+    DeviceGuard g(ctx->device);
+    int64_t bp = -1, bc = -1;
+    if (int rc = packets_common(ctx, static_cast<const uint8_t *>(d_arena), arena_len, pk, n, bpc, true,
+                                check_short_tail, &bp, &bc))
+        return rc;
+    if (bad_packet) *bad_packet = bp;
+    if (bad_chunk) *bad_chunk = bc;
+    // the verify result is in hand: only now is anything copied, and only what lies before the bad packet
+    const size_t good = bp >= 0 ? size_t(bp) : n;
+    std::vector<CopyRange> r(good);
+    uint64_t placed = 0;
+    for (size_t i = 0; i < good; ++i) {
+        r[i] = CopyRange{pk[i].data_off, dst_off + placed, pk[i].data_len};
+        placed += pk[i].data_len;
+    }
+    if (placed) {
+        if (int rc = gather_dev(ctx, d_dst, dst_len, d_arena, arena_len, r.data(), good)) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (delivered) *delivered = placed;
+    return 0;
 }
 
 int hdfs3_crc32c_verify_packet_stream_dev_async(hdfs3_crc_ctx *ctx, const void *d_arena, size_t arena_len,

@@ -188,4 +188,39 @@ BatchPlan plan_packet_batch(uint64_t arena, const DevPacket *h_pk, size_t n, uin
     return p;
 }
 
+size_t gather_first_bad(const CopyRange *in, size_t n, uint64_t src_len, uint64_t dst_len) {
+    for (size_t i = 0; i < n; ++i) {
+        const CopyRange &c = in[i];
+        if (c.src_off > src_len || c.len > src_len - c.src_off) return i;
+        if (c.dst_off > dst_len || c.len > dst_len - c.dst_off) return i;
+        if (c.len > (kGatherMaxTiles - 1) * kGatherTileBytes) return i;  // whatever the destination's alignment
+    }
+    return n;
+}
+
+size_t plan_gather_launch(uint64_t dst_addr, const CopyRange *in, size_t n, size_t pos, GatherLaunch *g) {
+    g->n = 0;
+    uint64_t tiles = 0;  // of the ranges before the last one
+    for (; pos < n; ++pos) {
+        const CopyRange &c = in[pos];
+        if (c.len == 0) continue;
+        if (g->n) {
+            CopyRange &p = g->r[g->n - 1];
+            const uint64_t merged = gather_tiles(dst_addr + p.dst_off, p.len + c.len);
+            if (p.src_off + p.len == c.src_off && p.dst_off + p.len == c.dst_off && tiles + merged <= kGatherMaxTiles) {
+                p.len += c.len;
+                g->tile_end[g->n - 1] = uint32_t(tiles + merged);
+                continue;
+            }
+            tiles = g->tile_end[g->n - 1];
+        }
+        const uint64_t t = gather_tiles(dst_addr + c.dst_off, c.len);
+        if (g->n == kGatherMaxRanges || tiles + t > kGatherMaxTiles) break;
+        g->r[g->n] = c;
+        g->tile_end[g->n] = uint32_t(tiles + t);
+        ++g->n;
+    }
+    return pos;
+}
+
 }  // namespace hdfs3crc

@@ -120,4 +120,37 @@ struct BatchPlan {
 BatchPlan plan_packet_batch(uint64_t arena, const DevPacket *h_pk, size_t n, uint32_t bpc, const uint64_t *arena_len,
                             bool have_pieces, int variant, DevSegment *h_stage);
 
+// ---- range gather (crc32c_gather.hip) -------------------------------------------------------------
+// One byte range of a gather: len bytes from src + src_off to dst + dst_off (mirrors hdfs3_copy_range).
+struct CopyRange {
+    uint64_t src_off, dst_off, len;
+};
+// A gather launch carries its ranges in the kernel arguments: at most this many (a default reader batch
+// of 64 packets is one launch); longer lists take more launches
+constexpr uint32_t kGatherMaxRanges = 64;
+// A workgroup's tile: kGatherThreads lanes x kGatherLinesPerLane destination lines of 16 bytes. A range's
+// lines are the aligned 16-byte lines of the destination that hold any of its bytes, so its first and
+// last line may be partial (the kernel writes those with byte stores)
+constexpr uint32_t kGatherThreads = 256;
+constexpr uint32_t kGatherLinesPerLane = 4;
+constexpr uint64_t kGatherTileBytes = uint64_t(kGatherThreads) * kGatherLinesPerLane * 16;
+constexpr uint64_t kGatherMaxTiles = (uint64_t(1) << 31) - 1;  // a launch's grid
+struct GatherLaunch {
+    CopyRange r[kGatherMaxRanges];
+    uint32_t tile_end[kGatherMaxRanges];  // tiles of ranges 0 .. i: workgroup w copies range i, tile_end[i-1] <= w < tile_end[i]
+    uint32_t n;
+};
+// tiles of a range whose first destination byte is at address dst_addr
+constexpr uint64_t gather_tiles(uint64_t dst_addr, uint64_t len) {
+    return len ? (((dst_addr & 15) + len + 15) / 16 * 16 + kGatherTileBytes - 1) / kGatherTileBytes : 0;
+}
+// Index of the first range that leaves [0, src_len) or [0, dst_len) or has more than kGatherMaxTiles
+// tiles, n when every range is inside (empty ranges are checked like the others)
+size_t gather_first_bad(const CopyRange *in, size_t n, uint64_t src_len, uint64_t dst_len);
+// Fills *g from in[pos ..) for a destination at address dst_addr and returns the position it stopped at
+// (n: this was the last launch): empty ranges dropped, a range that continues its predecessor on both
+// sides merged into it, closed at kGatherMaxRanges ranges or kGatherMaxTiles tiles. g->n may be 0 (nothing
+// but empty ranges were left). The ranges were checked by gather_first_bad.
+size_t plan_gather_launch(uint64_t dst_addr, const CopyRange *in, size_t n, size_t pos, GatherLaunch *g);
+
 }  // namespace hdfs3crc

@@ -269,6 +269,32 @@ class CrcContext:
               self._lib.hdfs3_crc32c_compute_packets_dev_async(self.ctx, d_arena, arena_len, self._descs(pk), len(pk),
                                                                bpc))
 
+    # -- range gather -----------------------------------------------------------------
+    @staticmethod
+    def _ranges(ranges) -> ctypes.Array:
+        if isinstance(ranges, ctypes.Array):  # built once by the caller (timed loops)
+            return ranges
+        arr = (_native.CopyRange * max(len(ranges), 1))()
+        for i, (src_off, dst_off, n) in enumerate(ranges):
+            arr[i].src_off, arr[i].dst_off, arr[i].len = src_off, dst_off, n
+        return arr
+
+    def gather_dev(self, d_dst: int, dst_len: int, d_src: int, src_len: int, ranges) -> None:
+        """hdfs3_gather_dev_async: ranges = [(src_off, dst_off, len)], enqueued on the ctx stream."""
+        self._check("hdfs3_gather_dev_async",
+              self._lib.hdfs3_gather_dev_async(self.ctx, d_dst, dst_len, d_src, src_len, self._ranges(ranges),
+                                               len(ranges)))
+
+    def verify_packets_gather_dev(self, d_arena: int, arena_len: int, pk, bpc: int, d_dst: int, dst_len: int,
+                                  dst_off: int = 0, check_short_tail: bool = False):
+        """hdfs3_crc32c_verify_packets_gather_dev: (bad_packet, bad_chunk, delivered)."""
+        bp, bc, placed = c_int64(-2), c_int64(-2), ctypes.c_uint64(0)
+        self._check("hdfs3_crc32c_verify_packets_gather_dev",
+              self._lib.hdfs3_crc32c_verify_packets_gather_dev(self.ctx, d_arena, arena_len, self._descs(pk), len(pk),
+                                                               bpc, int(check_short_tail), d_dst, dst_len, dst_off,
+                                                               byref(bp), byref(bc), byref(placed)))
+        return bp.value, bc.value, placed.value
+
     @staticmethod
     def packet_stream(crc_off: int, data_off: int, pitch: int, n: int, data_len: int, last_len: int | None = None):
         """hdfs3_pkt_stream: packet i's words at crc_off + i*pitch, data at data_off + i*pitch."""
@@ -384,6 +410,20 @@ class BlockReader:
                 break
             pos += got
         return out[:pos]
+
+    def read_into_device(self, d_buf: int, n: int) -> int:
+        """hdfs3_block_reader_read_dev: up to n verified bytes to the device address d_buf (memory of the
+        reader's device, e.g. a torch tensor's data_ptr()); returns bytes (0 = end of range)."""
+        got = self._lib.hdfs3_block_reader_read_dev(self.r, d_buf, min(n, 0x7FFFFFFF))
+        if got < 0:
+            check("hdfs3_block_reader_read_dev", got)
+        return got
+
+    def device_stats(self):
+        launches, placed = ctypes.c_uint64(), ctypes.c_uint64()
+        check("hdfs3_block_reader_device_stats",
+              self._lib.hdfs3_block_reader_device_stats(self.r, byref(launches), byref(placed)))
+        return {"gather_launches": launches.value, "bytes_gathered": placed.value}
 
     def stats(self):
         from ctypes import c_uint32, c_uint64
@@ -523,6 +563,14 @@ class InputStream:
     def pread_into(self, pos: int, out: np.ndarray, offset: int = 0, n: int | None = None) -> int:
         n = out.nbytes - offset if n is None else n
         return self._posix("hdfsPread", self._lib.hdfs3_input_pread(self.s, pos, out.ctypes.data + offset, n))
+
+    def read_into_device(self, d_buf: int, n: int) -> int:
+        """hdfs3_input_read_dev: hdfsRead with the destination at the device address d_buf."""
+        return self._posix("hdfs3_input_read_dev", self._lib.hdfs3_input_read_dev(self.s, d_buf, n))
+
+    def pread_into_device(self, pos: int, d_buf: int, n: int) -> int:
+        """hdfs3_input_pread_dev: hdfsPread with the destination at the device address d_buf."""
+        return self._posix("hdfs3_input_pread_dev", self._lib.hdfs3_input_pread_dev(self.s, pos, d_buf, n))
 
     def read_fully(self, length: int, chunk: int = 4 << 20) -> np.ndarray:
         out = np.empty(length, dtype=np.uint8)
