@@ -260,6 +260,26 @@ typedef struct hdfs3_append_info {
 int hdfs3_output_open_append(const hdfs3_writer_opts *opts, const hdfs3_append_info *append, hdfs3_packet_sink sink,
                              void *user, hdfs3_output_stream **out);
 int32_t hdfs3_output_write(hdfs3_output_stream *s, const void *buf, int32_t len);  /* hdfsWrite: len or -1 */
+/* hdfs3_output_write with the source in DEVICE memory: d_buf is memory of the stream's device
+ * (opts->device), e.g. a torch tensor's data_ptr(). The packet sequence is hdfs3_output_write's for the
+ * same bytes in the same call sequence (one append accounting serves both): tell(), flush, sync, close,
+ * block ends, append mode and the partial chunk re-sent after a flush are unchanged, and every packet the
+ * sink receives is byte-identical. write and write_dev may be mixed freely on one stream, inside one
+ * packet and inside one chunk.
+ * The bytes go from d_buf to the batch arena's device copy in one range-gather launch per batch touched
+ * (hdfs3_gather_dev_async's kernel), where the batch's CRC launch reads them; no host bounce copy and no
+ * upload of them is made. A batch that holds device-sourced bytes copies those bytes back to its pinned
+ * arena with its CRC words, since the sink is handed host packets. A stream that never calls write_dev
+ * issues the copies and launches it always did.
+ * When the call returns the source has been read and may be overwritten at once: the call waits on an
+ * event behind its last placement launch (one wait per call: many small calls pay it each time), not
+ * for the stream to drain. The source is never written.
+ * Returns len, or -1 + errno: EINVAL for NULL, len <= 0 or a pointer that is not memory of the stream's
+ * device (the stream stays usable, nothing was appended); EIO on a failed stream; a failing sink fails
+ * the stream as in hdfs3_output_write, after the placements already enqueued have completed. */
+int32_t hdfs3_output_write_dev(hdfs3_output_stream *s, const void *d_buf, int32_t len);
+/* placement launches made by write_dev so far and the bytes it took from device memory; 0 or -errno */
+int hdfs3_output_device_stats(hdfs3_output_stream *s, uint64_t *scatter_launches, uint64_t *bytes_from_device);
 int hdfs3_output_flush(hdfs3_output_stream *s);    /* hdfsFlush / hdfsHFlush: flushInternal(false) */
 int hdfs3_output_sync(hdfs3_output_stream *s);     /* hdfsSync: flushInternal(true)               */
 int64_t hdfs3_output_tell(hdfs3_output_stream *s);

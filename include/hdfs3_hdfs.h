@@ -114,6 +114,11 @@ int hdfs3_fs_set_readahead(hdfsFS fs, int blocks, int64_t max_bytes_per_block);
  * copy of them is made. Both kinds of read may be mixed on one hdfsFile. */
 tSize hdfs3_fs_read_dev(hdfsFS fs, hdfsFile file, void *d_buffer, tSize length);
 tSize hdfs3_fs_pread_dev(hdfsFS fs, hdfsFile file, void *d_buffer, tSize length, tOffset position);
+/* hdfsWrite with the source in DEVICE memory (hdfs3_output_write_dev in hdfs3_client.h), over sinks and
+ * pipelines alike: d_buffer is memory of the GPU the fs's write_opts name. Returns length, or -1 + errno
+ * as hdfsWrite (EINVAL also for a pointer that is not that GPU's memory). The source has been read when
+ * the call returns and is never written. hdfsWrite and this call may be mixed on one hdfsFile. */
+tSize hdfs3_fs_write_dev(hdfsFS fs, hdfsFile file, const void *d_buffer, tSize length);
 
 #ifdef __cplusplus
 }

@@ -248,6 +248,8 @@ CLIENT_API = {
     "hdfs3_local_reader_close": (c_int, [c_void_p]),
     "hdfs3_output_open": (c_int, [POINTER(WriterOpts), PACKET_SINK, c_void_p, POINTER(c_void_p)]),
     "hdfs3_output_write": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_output_write_dev": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_output_device_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "hdfs3_output_flush": (c_int, [c_void_p]),
     "hdfs3_output_sync": (c_int, [c_void_p]),
     "hdfs3_output_tell": (c_int64, [c_void_p]),
@@ -295,6 +297,7 @@ HDFS_API = {
     "hdfs3_fs_set_readahead": (c_int, [c_void_p, c_int, c_int64]),
     "hdfs3_fs_read_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32]),
     "hdfs3_fs_pread_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32, c_int64]),
+    "hdfs3_fs_write_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32]),
     "hdfs3_fs_set_append_stamp": (c_int, [c_void_p, ctypes.c_char_p, c_uint64]),
     "hdfs3_fs_set_block_size": (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_int64]),
 }

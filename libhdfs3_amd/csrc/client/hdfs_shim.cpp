@@ -472,6 +472,14 @@ tSize hdfsWrite(hdfsFS fs, hdfsFile file, const void *buffer, tSize length) {
     return length;
 }
 
+// hdfsWrite from device memory (not in hdfs.h): same checks, return and errno
+tSize hdfs3_fs_write_dev(hdfsFS fs, hdfsFile file, const void *d_buffer, tSize length) {
+    PARAMETER_ASSERT(fs && file && d_buffer && length > 0, -1, EINVAL);
+    PARAMETER_ASSERT(!file->input, -1, EINVAL);
+    if (hdfs3_output_write_dev(file->out, d_buffer, length) < 0) return stream_failed(tSize(-1));
+    return length;
+}
+
 int hdfsFlush(hdfsFS fs, hdfsFile file) {
     PARAMETER_ASSERT(fs && file, -1, EINVAL);
     return hdfsHFlush(fs, file);

@@ -13,6 +13,15 @@
 // while the GPU computes the other. When a batch completes, each packet's words are
 // copied in front of its data, its header in front of those, and the contiguous packet
 // [header][words][data] — byte-identical to Packet::getBuffer — goes to the sink in order.
+//
+// hdfs3_output_write_dev takes the bytes from device memory instead: the same append accounting, but
+// where write() memcpys into the pinned arena, write_dev() notes a range {offset in the caller's buffer,
+// offset in the arena, length}; the ranges of one batch go to the arena's DEVICE copy in one gather launch
+// (crc32c_gather.hip), and the call returns after an event behind its last launch. Each batch keeps a
+// ledger of the ranges the host wrote and the ranges placed (batch_ledger.h): dispatch uploads only the
+// former, runs the same packet compute over the arena, and copies the latter back into the pinned arena
+// with the CRC words, so emit() and the sink see host packets as before. A batch without placed bytes
+// issues exactly the one upload it always did.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +32,7 @@
 #include <vector>
 
 #include "../ctx.h"
+#include "batch_ledger.h"
 #include "hdfs3_client.h"
 #include "hdfs3_crc.h"
 #include "wire.h"
@@ -54,6 +64,7 @@ struct WBatch {
     PacketArena a;
     std::vector<Pkt> pk;
     uint64_t chunks = 0;      // CRC words of the dispatched packets
+    BatchLedger ledger;       // which bytes of the arena the host wrote, which were placed from the device
     bool dispatched = false;
 };
 
@@ -107,10 +118,23 @@ struct hdfs3_output_stream {
     Pkt *cur = nullptr;              // packet being filled (last slot of batch[cur_batch])
     uint64_t packets = 0, batches = 0;
 
+    // write_dev: the current call's source and its ranges into batch[cur_batch] not yet launched
+    const uint8_t *dev_src = nullptr;
+    uint64_t dev_src_len = 0;
+    std::vector<CopyRange> dev_pending;
+    bool dev_enqueued = false;       // placements launched and not yet known complete
+    hipEvent_t dev_done = nullptr;   // recorded behind a call's last placement launch
+    uint64_t dev_launches = 0, dev_bytes = 0;
+    std::vector<ByteRange> span;     // dispatch's copy lists
+    // the partial chunk a flush re-sends: where it lies in the host arena, taken into `carry` once the
+    // batch has been drained (placed bytes reach the host arena only with the batch's copy back)
+    const uint8_t *carry_from = nullptr;
+
     ~hdfs3_output_stream() {
         if (ctx) {
             (void)hipStreamSynchronize(ctx->stream);
             for (WBatch &b : batch) b.a.release();
+            if (dev_done) (void)hipEventDestroy(dev_done);
             ctx_release(ctx);
         }
     }
@@ -148,8 +172,32 @@ struct hdfs3_output_stream {
     }
 
     // ---- batches ----------------------------------------------------------------------------
+    // write_dev: the noted ranges go from the caller's buffer to the current batch's device arena, one
+    // launch per kGatherMaxRanges. Nothing past the slots' data regions can be written (dst_len).
+    int place_pending() {
+        if (dev_pending.empty()) return 0;
+        unsigned launched = 0;
+        const int rc = gather_dev(ctx, batch[cur_batch].a.d, crc_region, dev_src, dev_src_len, dev_pending.data(),
+                                  dev_pending.size(), &launched);
+        dev_pending.clear();
+        dev_launches += launched;
+        if (launched) dev_enqueued = true;
+        return rc;
+    }
+
+    // the source has been read once the placements completed: an event behind the last one, not a drain
+    // of the stream
+    int wait_placed() {
+        if (!dev_enqueued) return 0;
+        dev_enqueued = false;
+        HIP_OK(hipEventRecord(dev_done, ctx->stream));
+        HIP_OK(hipEventSynchronize(dev_done));
+        return 0;
+    }
+
     int dispatch(WBatch &b) {
         if (b.dispatched || b.pk.empty()) return 0;
+        if (int rc = place_pending()) return rc;  // only the current batch is ever dispatched with ranges noted
         b.dispatched = true;
         ++batches;
         size_t n = 0;
@@ -164,11 +212,22 @@ struct hdfs3_output_stream {
         }
         b.chunks = chunks;
         if (n) {
-            HIP_OK(hipMemcpyAsync(b.a.d + lo, b.a.h + lo, hi - lo, hipMemcpyHostToDevice, ctx->stream));
+            if (!b.ledger.any_device()) {
+                HIP_OK(hipMemcpyAsync(b.a.d + lo, b.a.h + lo, hi - lo, hipMemcpyHostToDevice, ctx->stream));
+            } else {  // around the placed bytes, which the host arena does not hold
+                b.ledger.uploads(&span);
+                for (const ByteRange &r : span)
+                    HIP_OK(hipMemcpyAsync(b.a.d + r.off, b.a.h + r.off, r.len, hipMemcpyHostToDevice, ctx->stream));
+            }
             // the batch's own piece scratch (bpc = R x 4096 batches of whole-round packets: pieces + combine)
             HIP_OK(launch_packet_batch(launch_env(ctx, &b.a.pieces), b.a.d, hp, n, bpc, false, 0, nullptr, b.a.h_desc,
                                        b.a.d_desc));
             ++ctx->launches;
+            if (b.ledger.any_device()) {  // the sink is handed host packets
+                b.ledger.downloads(&span);
+                for (const ByteRange &r : span)
+                    HIP_OK(hipMemcpyAsync(b.a.h + r.off, b.a.d + r.off, r.len, hipMemcpyDeviceToHost, ctx->stream));
+            }
             HIP_OK(hipMemcpyAsync(b.a.h + crc_region, b.a.d + crc_region, 4 * chunks, hipMemcpyDeviceToHost,
                                   ctx->stream));
         }
@@ -206,6 +265,7 @@ struct hdfs3_output_stream {
             }
         }
         b.pk.clear();
+        b.ledger.clear();
         b.dispatched = false;
         return error;
     }
@@ -234,6 +294,7 @@ struct hdfs3_output_stream {
         p->block_index = block_index;
         if (position) {  // the flushed partial chunk opens the new packet again
             std::memcpy(batch[cur_batch].a.h + p->data_off, carry.data(), position);
+            batch[cur_batch].ledger.host(p->data_off, position);
             p->data_len = position;
         }
         cur = p;
@@ -243,8 +304,7 @@ struct hdfs3_output_stream {
     // sendPacket: the packet is complete; it leaves with its batch
     void send_current() {
         pipeline_open = true;
-        if (position && cur) std::memcpy(carry.data(), batch[cur_batch].a.h + cur->data_off + cur->data_len - position,
-                                         position);
+        if (position && cur) carry_from = batch[cur_batch].a.h + cur->data_off + cur->data_len - position;
         cur = nullptr;
     }
 
@@ -269,11 +329,17 @@ struct hdfs3_output_stream {
         WBatch &a = batch[cur_batch ^ 1], &b = batch[cur_batch];
         if (int rc = emit(a)) return rc;  // dispatched earlier, so it goes first
         if (int rc = dispatch(b)) return rc;
-        return emit(b);
+        if (int rc = emit(b)) return rc;
+        if (carry_from) {  // both arenas are whole in host memory now, and no slot has been reused yet
+            std::memcpy(carry.data(), carry_from, position);
+            carry_from = nullptr;
+        }
+        return 0;
     }
 
-    // appendInternal (:298-346)
-    int append(const uint8_t *buf, int64_t size) {
+    // appendInternal (:298-346). dev: buf is device memory (write_dev); only where the bytes are copied
+    // differs, the accounting is this one loop for both
+    int append(const uint8_t *buf, int64_t size, bool dev = false) {
         int64_t todo = size;
         while (todo > 0) {
             if (!cur)
@@ -286,7 +352,14 @@ struct hdfs3_output_stream {
             const int64_t pkt_room = int64_t(cpp_cur) * cs - cur->data_len;
             const int64_t blk_room = block_size - bytes_written - position;
             const uint32_t n = uint32_t(std::min({todo, pkt_room, blk_room}));
-            std::memcpy(batch[cur_batch].a.h + cur->data_off + cur->data_len, buf + (size - todo), n);
+            const uint64_t at = cur->data_off + cur->data_len;
+            if (dev) {
+                dev_pending.push_back(CopyRange{uint64_t(size - todo), at, n});
+                batch[cur_batch].ledger.device(at, n);
+            } else {
+                std::memcpy(batch[cur_batch].a.h + at, buf + (size - todo), n);
+                batch[cur_batch].ledger.host(at, n);
+            }
             cur->data_len += n;
             todo -= n;
             bytes_written += int64_t((position + n) / cs) * cs;
@@ -438,6 +511,53 @@ int32_t hdfs3_output_write(hdfs3_output_stream *s, const void *buf, int32_t len)
     if (int rc = s->append(static_cast<const uint8_t *>(buf), len))
         return posix_fail(-rc, s->error ? s->error_msg : std::string(hdfs3_crc_last_error()));
     return len;
+}
+
+int32_t hdfs3_output_write_dev(hdfs3_output_stream *s, const void *d_buf, int32_t len) {
+    if (!s || !d_buf || len <= 0) return posix_fail(EINVAL, "hdfs3_output_write_dev: invalid argument");
+    if (s->error) return posix_fail(EIO, s->error_msg);
+    DeviceGuard g(s->ctx->device);
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, d_buf) != hipSuccess || at.type != hipMemoryTypeDevice ||
+        at.device != s->ctx->device) {
+        (void)hipGetLastError();  // a host pointer is the caller's mistake, not a fault of the GPU
+        return posix_fail(EINVAL, "hdfs3_output_write_dev: the buffer is not device memory of device " +
+                                      std::to_string(s->ctx->device));
+    }
+    if (!s->dev_done) {
+        const hipError_t e = hipEventCreateWithFlags(&s->dev_done, hipEventDisableTiming);
+        if (e != hipSuccess) return posix_fail(EIO, std::string("hipEventCreateWithFlags: ") + hipGetErrorString(e));
+    }
+    s->dev_src = static_cast<const uint8_t *>(d_buf);
+    s->dev_src_len = uint64_t(len);
+    int rc = s->append(s->dev_src, len, true);
+    if (!rc) rc = s->place_pending();
+    std::string msg;
+    if (rc) msg = s->error ? s->error_msg : std::string(hdfs3_crc_last_error());
+    // also after a failure in the middle (a failing sink): the placements already enqueued still read the
+    // source, so they are waited for before the caller gets it back
+    const int wrc = s->wait_placed();
+    if (wrc && !rc) {
+        rc = wrc;
+        msg = hdfs3_crc_last_error();
+    }
+    s->dev_pending.clear();
+    s->dev_src = nullptr;
+    s->dev_src_len = 0;
+    if (rc) {
+        // ranges the ledger counts as placed may never have been launched: the stream cannot go on
+        if (!s->error) s->sticky(rc, msg);
+        return posix_fail(-rc, msg);
+    }
+    s->dev_bytes += uint64_t(len);
+    return len;
+}
+
+int hdfs3_output_device_stats(hdfs3_output_stream *s, uint64_t *scatter_launches, uint64_t *bytes_from_device) {
+    if (!s) return fail(-EINVAL, "null stream");
+    if (scatter_launches) *scatter_launches = s->dev_launches;
+    if (bytes_from_device) *bytes_from_device = s->dev_bytes;
+    return 0;
 }
 
 int hdfs3_output_flush(hdfs3_output_stream *s) {

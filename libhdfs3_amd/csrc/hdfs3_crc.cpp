@@ -769,7 +769,11 @@ void hdfs3_crc_ctx_release(hdfs3_crc_ctx *ctx) { hdfs3crc::ctx_release(ctx); }
 int hdfs3_crc_pool_stats_get(hdfs3_crc_pool_stats *out) {
     if (!out) return fail(-EINVAL, "null out");
     hdfs3_crc_pool_stats st{};
-    // the short-circuit readers' pooled contexts and windows are part of the same budget
+    // The short-circuit readers' pooled contexts and windows are part of the same budget. The two pools
+    // are read one after the other: without the admission lock an entry taken out of the first and a ctx
+    // admitted into the second in between were both counted, a sum above the cap that never existed. With
+    // it only removals can fall between the two reads, so the sum is at most what was retained.
+    std::lock_guard<std::mutex> adm(hdfs3crc::pool_admission_mu());
     const hdfs3crc::LocalPoolStats lp = hdfs3crc::local_pool_stats();
     std::lock_guard<std::mutex> lk(hdfs3crc::g_ctx_pool_mu);
     for (hdfs3_crc_ctx *c : hdfs3crc::g_ctx_pool) {

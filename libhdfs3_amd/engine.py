@@ -679,6 +679,17 @@ class OutputStream:
         buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data)
         return self._posix("hdfsWrite", self._lib.hdfs3_output_write(self.s, buf.ctypes.data, buf.nbytes))
 
+    def write_device(self, d_ptr: int, n: int) -> int:
+        """hdfs3_output_write_dev: hdfsWrite of the n bytes at the device address d_ptr (memory of the
+        stream's device). The source has been read when the call returns."""
+        return self._posix("hdfs3_output_write_dev", self._lib.hdfs3_output_write_dev(self.s, d_ptr, n))
+
+    def device_stats(self):
+        from ctypes import c_uint64
+        launches, nbytes = c_uint64(), c_uint64()
+        check("hdfs3_output_device_stats", self._lib.hdfs3_output_device_stats(self.s, byref(launches), byref(nbytes)))
+        return {"scatter_launches": launches.value, "bytes_from_device": nbytes.value}
+
     def flush(self) -> None:
         self._posix("hdfsFlush", self._lib.hdfs3_output_flush(self.s))
 

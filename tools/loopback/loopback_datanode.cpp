@@ -37,6 +37,7 @@
 #include <thread>
 #include <unistd.h>
 
+#include "../../include/hdfs3_client.h"
 #include "../../libhdfs3_amd/csrc/client/net.h"
 #include "../../libhdfs3_amd/csrc/client/wire.h"
 #include "../../libhdfs3_amd/csrc/md5.h"
@@ -597,6 +598,22 @@ int hdfs3_loopback_count_sink(void *user, const void *pkt, size_t len, const voi
     c[0] += 1;
     c[1] += len;
     c[2] += x & 1;  // keeps the loop
+    return 0;
+}
+
+/* Test/bench packet sink that checks what it is handed: user = uint64_t[6] {address of the source bytes,
+ * position in them, packets, wire bytes, packets whose data differ from the source at the position,
+ * their first seqno + 1}. Every packet's data region is compared whole (tools/write_dev_ab.py). */
+int hdfs3_loopback_compare_sink(void *user, const void *pkt, size_t len, const hdfs3_packet_info *info) {
+    uint64_t *c = static_cast<uint64_t *>(user);
+    const uint8_t *src = reinterpret_cast<const uint8_t *>(uintptr_t(c[0]));
+    const size_t head = size_t(wire::kPacketHeaderSize) + 4u * size_t(info->num_chunks);
+    const bool ok = len == head + size_t(info->data_len) &&
+                    std::memcmp(static_cast<const uint8_t *>(pkt) + head, src + c[1], size_t(info->data_len)) == 0;
+    c[1] += uint64_t(info->data_len);
+    c[2] += 1;
+    c[3] += len;
+    if (!ok && !c[4]++) c[5] = uint64_t(info->seqno) + 1;
     return 0;
 }
 
