@@ -259,10 +259,16 @@ int hdfs3_crc32c_compute_packets_dev_async(hdfs3_crc_ctx *ctx, void *d_arena, si
 /* A packet stream at one pitch — the layout of a received-packet ring and of the block
  * reader's arenas: packet i's BE32 words at crc_off + i*pitch and its data at
  * data_off + i*pitch, data_len bytes each except the last (last_len <= data_len).
- * ONE launch with O(1) host work and no descriptor array: when data_len is a power-of-two
- * number of 4 KiB rounds (64 KiB packets: 16) at bpc 512..4096 with 16-B aligned data, the
- * wave kernel walks the packets directly (docs/DESIGN_HISTORY.md §4.2); any other stream is expanded into
- * descriptors once and takes the asynchronous descriptor path. Same result key; flags as
+ * ONE launch with O(1) host work and no descriptor array when the wave kernel can walk the
+ * packets directly (docs/DESIGN_HISTORY.md §4.2): bpc 512, 1024, 2048 or 4096, or a multiple of
+ * 4096 above it (4 KiB piece CRCs and a combine); packet 0's data 16-B aligned, its words 4-B
+ * aligned and the pitch a multiple of 16; every packet but the last whole chunks (data_len a
+ * multiple of bpc, any number of 4 KiB rounds, the last one may be partial); at least one whole
+ * chunk in the stream and fewer than 2^31 4 KiB units. The last packet may be any length up to
+ * data_len, 0 included when n > 1. Any other stream is expanded into descriptors once and takes
+ * the asynchronous descriptor path. With n == 1 the stream is the last_len bytes at data_off and
+ * their words at crc_off: pitch and data_len address nothing (pitch may be 0; one that is not a
+ * multiple of 16 only sends the stream to the descriptor path). Same result key; flags as
  * hdfs3_crc32c_verify_dev_async_ex (HDFS3_LAUNCH_OVERLAP_PREVIOUS under the same contract). */
 typedef struct hdfs3_pkt_stream {
     uint64_t crc_off;   /* packet 0's CRC region                        */

@@ -11,12 +11,20 @@ bool packet_geom(uint64_t data_len, uint64_t last_len, uint64_t npk, uint32_t un
     if (npk == 0 || unit_bpc == 0 || unit_bpc > uint32_t(kRoundBytes) || last_len > data_len) return false;
     if (npk > 1 && (data_len == 0 || data_len % unit_bpc)) return false;  // only the last packet ends short
     PacketGeom r;
-    r.pk_len = npk > 1 ? data_len : 0;
-    r.upp = uint32_t(npk > 1 ? (data_len + kRoundBytes - 1) / kRoundBytes : 1);
-    r.ptail = uint32_t(npk > 1 ? data_len - uint64_t(r.upp - 1) * kRoundBytes : kRoundBytes);
     const uint64_t lw = last_len / unit_bpc * unit_bpc;
     r.lunits = uint32_t((lw + kRoundBytes - 1) / kRoundBytes);
     r.ltail = r.lunits ? uint32_t(lw - uint64_t(r.lunits - 1) * kRoundBytes) : 0;
+    if (npk > 1) {
+        r.pk_len = data_len;
+        r.upp = uint32_t((data_len + kRoundBytes - 1) / kRoundBytes);
+        r.ptail = uint32_t(data_len - uint64_t(r.upp - 1) * kRoundBytes);
+    } else {
+        // one packet is its own last packet: with upp = lunits every unit u < lunits is round u of
+        // packet 0 (u / upp = 0), whatever data_len and the pitch are
+        r.pk_len = 0;
+        r.upp = r.lunits;
+        r.ptail = r.ltail;
+    }
     const uint64_t units = (npk - 1) * uint64_t(r.upp) + r.lunits;
     if (units == 0 || units >= (uint64_t(1) << 31)) return false;
     // q = (u * magic) >> shift = u / upp for every u < 2^31: magic = ceil(2^(31 + l) / upp), l =

@@ -39,8 +39,8 @@ struct PacketGeom {
 };
 // Fills g for npk packets of data_len bytes (the last last_len) with chunks of unit_bpc bytes
 // (<= 4096; callers at bpc = R x 4096 pass 4096). False when it does not fit the walk: a non-last
-// packet that ends in a short chunk, no unit at all, or 2^31 units or more.
-// Open finding: npk == 1 with last_len above one round gets upp = 1.
+// packet that ends in a short chunk, no unit at all, or 2^31 units or more. One packet (npk == 1) is
+// its own last packet: upp = lunits, ptail = ltail and pk_len = 0, so every unit is a round of packet 0.
 bool packet_geom(uint64_t data_len, uint64_t last_len, uint64_t npk, uint32_t unit_bpc, PacketGeom *g);
 
 // Packet-descriptor as seen by the device (mirrors hdfs3_pkt_desc).

@@ -111,15 +111,25 @@ void check_walks() {
             if (data_len >= 300) lasts.push_back(data_len - 300);
             for (uint64_t last_len : lasts) {
                 if (last_len > data_len) continue;
-                for (uint64_t npk : {2, 3, 64, 4097}) check_walk(bpc, npk, data_len, last_len);
-                // One packet: only up to one round. npk == 1 with last_len above 4096 is the open
-                // round-6 finding (packet_geom gives such a stream upp = 1, so unit u maps to packet
-                // u); fixing it is a change of its own, and these cases join the list then.
-                if (last_len <= uint64_t(kRoundBytes)) check_walk(bpc, 1, data_len, last_len);
+                // one packet: every unit is a round of packet 0, whatever its length
+                for (uint64_t npk : {1, 2, 3, 64, 4097}) check_walk(bpc, npk, data_len, last_len);
             }
         }
+        // one packet of many rounds that ends inside a chunk (a non-last packet could not)
+        check_walk(bpc, 1, 131072, 131072 - 7);
+        check_walk(bpc, 1, 65536, 65024 - 11);
     }
+    // chunks of R x 4096: the pieces path plans its 4096-byte pieces with unit_bpc 4096 whatever R is,
+    // so a one-packet stream's pieces are the whole rounds of last_len
+    for (uint64_t last_len : {uint64_t(4096), uint64_t(4096 + 8192), uint64_t(4096 * 5 + 100), uint64_t(65024 - 11),
+                              uint64_t(65536 - 300), uint64_t(65536)})
+        check_walk(4096, 1, 65536, last_len);
+    check_walk(4096, 1, 131072, 131072 - 7);
     PacketGeom g;
+    // a one-packet stream has the last packet's geometry: no unit can map past packet 0
+    CHECK(packet_geom(65536, 65536 - 300, 1, 512, &g) && g.upp == 16 && g.lunits == 16 && g.ptail == g.ltail &&
+              g.ltail == 4096 - 512 && g.pk_len == 0,
+          "one packet: upp %u lunits %u ptail %u ltail %u", g.upp, g.lunits, g.ptail, g.ltail);
     CHECK(!packet_geom(65536 - 300, 100, 2, 512, &g), "a non-last packet that is not whole chunks");
     CHECK(!packet_geom(65536, 65536, 0, 512, &g), "npk = 0");
     CHECK(!packet_geom(65536, 65537, 2, 512, &g), "last_len > data_len");
@@ -252,6 +262,22 @@ void check_routes() {
     EXPECT_ROUTE(plan(wire, 512, true, 0, &whole), Route::kPitchStream);
     // before: 718 (bad_index == null): no check at all
     EXPECT_ROUTE(plan(wire, 512, true, 0, nullptr), Route::kPitchStream);
+    // the stream API's one-packet streams: the walk takes them at any 16-byte pitch, 0 included, with the
+    // last packet's geometry (at R x 4096: its 4096-byte pieces); an unaligned pitch goes to descriptors
+    const void *const data = reinterpret_cast<const void *>(uintptr_t(kArena + 512));
+    const void *const words = reinterpret_cast<const void *>(uintptr_t(kArena));
+    for (uint64_t pitch : {uint64_t(0), uint64_t(16), kSlot}) {
+        PitchStream s;
+        CHECK(plan_packet_stream(65536, 65536 - 300, 1, 512, data, words, pitch, true, 0, &s) && s.npk == 1 &&
+                  s.last_len == 65536 - 300 && s.geom.upp == 16 && s.geom.lunits == 16 && s.geom.pk_len == 0,
+              "one packet at pitch %llu: upp %u", (unsigned long long)pitch, s.geom.upp);
+        CHECK(plan_packet_stream(65536, 65536 - 300, 1, 12288, data, words, pitch, true, 0, &s) && s.geom.upp == 15 &&
+                  s.geom.lunits == 15 && s.geom.ltail == 4096 && s.geom.pk_len == 0,
+              "one packet of 12 KiB chunks at pitch %llu: upp %u", (unsigned long long)pitch, s.geom.upp);
+    }
+    PitchStream s;
+    CHECK(!plan_packet_stream(65536, 65536 - 300, 1, 512, data, words, 7, true, 0, &s), "one packet at pitch 7");
+    CHECK(!plan_packet_stream(65536, 100, 1, 512, data, words, 0, true, 0, &s), "one packet without a whole chunk");
 }
 
 }  // namespace
