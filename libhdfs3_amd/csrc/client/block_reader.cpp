@@ -40,6 +40,7 @@
 #include "block_reader.h"
 #include "hdfs3_crc.h"
 #include "net.h"
+#include "reader_layout.h"
 #include "wire.h"
 
 using namespace hdfs3crc;
@@ -50,7 +51,10 @@ constexpr int kDefaultBatchPackets = 64;
 constexpr int kDefaultTimeoutMs = 60000;  // input.read.timeout default (SessionConfig.cpp)
 constexpr size_t kMaxResponse = 10u << 20;  // RemoteBlockReader.cpp:116
 constexpr int kSlots = 3;                  // receiving / verifying / delivering
-constexpr int kPhases = 8;                 // hdfs3_reader_phase_ns
+// hdfs3_reader_phase_ns, in the order it documents (the first five: hdfs3x_block_reader_timing); round 6 added
+// the receiver's waits for a free slot, the caller's for a ready batch and the receiver thread's CPU time
+enum Phase { kPhaseRecv, kPhaseArena, kPhaseLaunch, kPhaseGpuWait, kPhaseCopyOut, kPhaseRxWaitFreeSlot,
+             kPhaseCallerWaitBatch, kPhaseReceiverCpu, kPhases };
 constexpr int kWaitPollUs = 20;            // the caller's sleep between queries of a batch's event
 std::atomic<uint64_t> g_phase_ns[kPhases] = {};
 
@@ -62,48 +66,23 @@ uint64_t thread_cpu_ns() {
 constexpr int kMaxSlots = 64;              // deepest ring (read-ahead of a whole block)
 constexpr int32_t kMaxPacketData = 16 << 20;  // PacketReceiver.MAX_PACKET_SIZE (Hadoop)
 constexpr size_t kArenaCacheMax = 6;       // arenas a ctx keeps for its next reader
-// a batch arena's room per packet: the datanode's default 64 KiB packet, its 128 words at bpc 512 and
-// the 16-byte alignment of its data (larger packets close a batch early; one that does not fit an
-// empty arena grows it). Round 4: 80 KiB before, so a 64-packet arena pinned 5 MiB for 4.03 MiB of
-// packets and a read-ahead stream's rings overran the pool's pinned cap by a ring (config 5)
-constexpr size_t kPacketGuess = 64 * 1024 + 512 + 16;
-
-struct PacketRef {
-    uint64_t data_off, crc_off;  // inside the arena
-    uint32_t data_len;
-    uint32_t skip;               // pendingAhead (RemoteBlockReader.cpp:264-266)
-    uint32_t deliver;            // bytes of this packet inside [start, end)
-};
 
 struct Batch {
     PacketArena a;
-    size_t used = 0;
-    std::vector<PacketRef> pk;
+    BatchLayout lay;     // where the packets are (reader_layout.h)
+    DeliveryCursor cur;  // where delivery stands
     bool verified = false;
     int64_t bad_pkt = -1;
-    size_t dpkt = 0, doff = 0;  // delivery cursor
-    // dense layout (round 5, see receive()): words of every packet back to back from offset 0, the
-    // packets' data back to back from d0; chunk0[i] = packet i's first chunk in the batch
-    bool dense = false, sealed = false;
-    uint64_t d0 = 0, words_used = 0, data_used = 0;
-    std::vector<uint64_t> chunk0;
     bool uploaded = false;  // the arena's device copy holds the batch (launch(), or read_dev for an unverified one)
 
     void reset() {
-        used = 0;
-        pk.clear();
-        verified = false;
+        lay.reset();
+        cur = DeliveryCursor();
+        verified = uploaded = false;
         bad_pkt = -1;
-        dpkt = doff = 0;
-        dense = sealed = false;
-        d0 = words_used = data_used = 0;
-        chunk0.clear();
-        uploaded = false;
     }
+    size_t limit() const { return bad_pkt >= 0 ? size_t(bad_pkt) : lay.pk.size(); }  // delivery stops here
 };
-
-// Chunk sizes the contiguous kernels take (launch_chunks); others keep the wire layout
-bool dense_bpc(uint32_t bpc) { return round_bpc(bpc) || pieces_bpc(bpc); }
 
 // HDFS3_READER_LAYOUT=wire keeps every batch in the wire layout (A/B measurement knob)
 bool wire_layout_forced() {
@@ -227,10 +206,7 @@ struct hdfs3_block_reader {
     std::atomic<uint64_t> packets{0}, batches{0};
     std::atomic<uint64_t> dev_launches{0}, dev_bytes{0};  // read_dev: gather launches, bytes they placed
     hipEvent_t dev_done = nullptr;                        // read_dev: recorded after a call's last gather
-    // receive, alloc, launch, wait, deliver (hdfs3x_block_reader_timing), then (round 6) the receiver's
-    // waits for a free slot, the caller's waits for a ready batch, the receiver thread's CPU time:
-    // summed into g_phase_ns when the reader closes (hdfs3_reader_phase_ns)
-    std::atomic<uint64_t> t_ns[kPhases] = {};
+    std::atomic<uint64_t> t_ns[kPhases] = {};  // summed into g_phase_ns when the reader closes
     // How the caller waits for a batch's verify (round 6). Default: it queries the batch's event and
     // sleeps kWaitPollUs between queries, leaving its core to the receivers and the datanode. Measured
     // on config 5 (profiles/r06): a blocking-sync hipEventSynchronize still spun inside the runtime (the
@@ -301,23 +277,20 @@ struct hdfs3_block_reader {
             have_pending_hdr = false;
             return 0;
         }
-        if (have_next_raw) {  // received with the previous packet's payload
-            have_next_raw = false;
-            if (!h.decode(next_raw, sizeof(next_raw))) return rx_fail(-EPROTO, "Invalid PacketHeader");
-            return 0;
-        }
-        uint8_t buf[wire::kPacketHeaderSize];
-        if (int rc = net::recv_fully(fd, buf, sizeof(buf)))
-            return rx_fail(rc, "RemoteBlockReader: failed to read block header");
-        if (!h.decode(buf, sizeof(buf))) return rx_fail(-EPROTO, "Invalid PacketHeader");
+        if (!have_next_raw)  // else it was received with the previous packet's payload
+            if (int rc = net::recv_fully(fd, next_raw, sizeof(next_raw)))
+                return rx_fail(rc, "RemoteBlockReader: failed to read block header");
+        have_next_raw = false;
+        if (!h.decode(next_raw, sizeof(next_raw))) return rx_fail(-EPROTO, "Invalid PacketHeader");
         return 0;
     }
 
     // readNextPacket (:226-277) for up to batch_packets packets into `b`
     int receive(Batch &b) {
-        Timer tm(t_ns[0]);
+        Timer tm(t_ns[kPhaseRecv]);
         b.reset();
-        while (int(b.pk.size()) < batch_packets && !range_done) {
+        BatchLayout &l = b.lay;
+        while (int(l.pk.size()) < batch_packets && !range_done) {
             wire::PacketHeader h;
             if (int rc = read_header(h)) return rc;
             if (!h.sanity_check(last_seqno)) return rx_fail(-EIO, "RemoteBlockReader: Packet failed on sanity check");
@@ -331,92 +304,34 @@ struct hdfs3_block_reader {
             if (h.data_len > kMaxPacketData) return rx_fail(-EIO, "Invalid Packet, dataLen exceeds 16 MiB");
             if (h.offset_in_block > recv_cursor || recv_cursor - h.offset_in_block >= h.data_len)
                 return rx_fail(-EIO, "Invalid Packet, offsetInBlock does not continue the block");
-            const uint64_t chunks = (uint64_t(h.data_len) + chunk_size - 1) / chunk_size;
-            const uint64_t crc_len = chunks * checksum_size;
+            const uint64_t crc_len = (uint64_t(h.data_len) + chunk_size - 1) / chunk_size * checksum_size;
             if (int64_t(h.packet_len) != 4 + int64_t(h.data_len) + int64_t(crc_len))
                 return rx_fail(-EIO, "Invalid Packet, packetLen does not match dataLen and checksums");
-            const uint64_t size = crc_len + uint64_t(h.data_len);
-            if (b.pk.empty())
-                b.dense = verify && checksum_size == 4 && dense_bpc(chunk_size) && !wire_layout_forced();
-            if (b.dense) {
-                // Dense layout (round 5): the socket's [words][data] of each packet land in two places,
-                // the words after the batch's earlier words, the data after its earlier data. While every
-                // packet but the last holds whole chunks, the batch is then ONE contiguous block with its
-                // own .meta-style word array, and the GPU verifies it with the contiguous round kernel
-                // (launch()): no packet pitch, no 4 KiB rounds straddling packets. Same bytes on the
-                // wire, same delivery (PacketRef), same ChecksumException semantics.
-                if (b.pk.empty()) {
-                    // room for batch_packets packets' words, sized for the largest packet expected (a
-                    // datanode's 64 KiB, or this one if larger): a short first packet must not
-                    // shrink the word region and close the batch after a few packets
-                    const uint64_t exp_data = std::max<uint64_t>(uint64_t(h.data_len), uint64_t(64) << 10);
-                    const uint64_t max_crc = (exp_data + chunk_size - 1) / chunk_size * checksum_size;
-                    b.d0 = (uint64_t(batch_packets) * max_crc + 4095) & ~uint64_t(4095);
-                    // the arena as acquired holds the batch (64 KiB packets: 32 KiB of words + 4 MiB of
-                    // data in the 64 x 66,064 B the ring is sized for); larger packets close the batch
-                    // early, as in the wire layout, and only a single packet that does not fit grows it
-                    const uint64_t need = b.d0 + uint64_t(h.data_len);
-                    if (need > b.a.cap)
-                        if (int rc = grow(b.a, need, size_t(batch_packets))) return rx_fail(rc, "arena growth failed");
-                } else if (b.sealed || b.words_used + crc_len > b.d0 ||
-                           b.d0 + b.data_used + uint64_t(h.data_len) > b.a.cap) {
-                    pending_hdr = h;  // close this batch; the header opens the next
-                    have_pending_hdr = true;
-                    break;
-                }
-                // the packet's checksums and data in one scatter read (:244-245 reads them as one buffer)
-                iovec v[3] = {{b.a.h + b.words_used, crc_len}, {b.a.h + b.d0 + b.data_used, size_t(h.data_len)},
-                              {next_raw, header_ahead ? sizeof(next_raw) : 0}};
-                if (int rc = net::recv_fully_iov(fd, v, 3))
-                    return rx_fail(rc, "RemoteBlockReader: failed to read packet payload");
-                have_next_raw = header_ahead;
-                last_seqno = h.seqno;
-                packets.fetch_add(1, std::memory_order_relaxed);
-                int64_t ahead = recv_cursor - h.offset_in_block;
-                ahead = ahead > 0 ? ahead : 0;
-                const int64_t useful =
-                    std::max<int64_t>(0, std::min<int64_t>(h.data_len - ahead, end_offset - recv_cursor));
-                b.pk.push_back(PacketRef{b.d0 + b.data_used, b.words_used, uint32_t(h.data_len), uint32_t(ahead),
-                                         uint32_t(useful)});
-                eager(b.a.h + b.d0 + b.data_used + ahead, useful);
-                b.chunk0.push_back(b.words_used / 4);
-                b.words_used += crc_len;
-                b.data_used += uint64_t(h.data_len);
-                b.used = b.d0 + b.data_used;
-                if (h.data_len % chunk_size) b.sealed = true;  // a short chunk ends the contiguous chunk run
-                const int64_t reached = recv_cursor + h.data_len - ahead;
-                recv_cursor = reached;
-                if (reached >= end_offset) {
-                    if (int rc = read_trailer()) return rc;
-                    range_done = true;
-                }
-                continue;
+            if (l.pk.empty())
+                l.open(uint32_t(h.data_len), chunk_size, checksum_size, batch_packets,
+                       verify && checksum_size == 4 && dense_bpc(chunk_size) && !wire_layout_forced());
+            const Placement p = l.place(uint32_t(h.data_len), crc_len, b.a.cap);
+            if (p.close) {  // the header opens the next batch
+                pending_hdr = h;
+                have_pending_hdr = true;
+                break;
             }
-            uint64_t off = ((b.used + crc_len + 15) & ~uint64_t(15)) - crc_len;
-            if (off + size > b.a.cap) {
-                if (!b.pk.empty()) {  // close this batch; the header opens the next
-                    pending_hdr = h;
-                    have_pending_hdr = true;
-                    break;
-                }
-                if (int rc = grow(b.a, size + 64, size_t(batch_packets))) return rx_fail(rc, "arena growth failed");
-                off = ((crc_len + 15) & ~uint64_t(15)) - crc_len;
-            }
-            iovec v[2] = {{b.a.h + off, size}, {next_raw, header_ahead ? sizeof(next_raw) : 0}};
-            if (int rc = net::recv_fully_iov(fd, v, 2))
+            if (p.need > b.a.cap)
+                if (int rc = grow(b.a, p.need, size_t(batch_packets))) return rx_fail(rc, "arena growth failed");
+            // the packet's checksums and data in one scatter read (:244-245 reads them as one buffer)
+            iovec v[3] = {{b.a.h + p.crc_off, crc_len}, {b.a.h + p.data_off, size_t(h.data_len)},
+                          {next_raw, header_ahead ? sizeof(next_raw) : 0}};
+            if (int rc = net::recv_fully_iov(fd, v, 3))
                 return rx_fail(rc, "RemoteBlockReader: failed to read packet payload");
             have_next_raw = header_ahead;
             last_seqno = h.seqno;
             packets.fetch_add(1, std::memory_order_relaxed);
-            int64_t ahead = recv_cursor - h.offset_in_block;
-            ahead = ahead > 0 ? ahead : 0;
+            const int64_t ahead = std::max<int64_t>(0, recv_cursor - h.offset_in_block);
             const int64_t useful = std::max<int64_t>(0, std::min<int64_t>(h.data_len - ahead, end_offset - recv_cursor));
-            b.pk.push_back(PacketRef{off + crc_len, off, uint32_t(h.data_len), uint32_t(ahead), uint32_t(useful)});
-            eager(b.a.h + off + crc_len + ahead, useful);
-            b.used = off + size;
-            const int64_t reached = recv_cursor + h.data_len - ahead;
-            recv_cursor = reached;
-            if (reached >= end_offset) {
+            l.commit(p, uint32_t(h.data_len), uint32_t(ahead), uint32_t(useful));
+            eager(b.a.h + p.data_off + ahead, useful);
+            recv_cursor += h.data_len - ahead;
+            if (recv_cursor >= end_offset) {
                 if (int rc = read_trailer()) return rc;
                 range_done = true;
             }
@@ -436,7 +351,7 @@ struct hdfs3_block_reader {
     }
 
     int launch(Batch &b) {
-        Timer tm(t_ns[2]);
+        Timer tm(t_ns[kPhaseLaunch]);
         batches.fetch_add(1, std::memory_order_relaxed);
         if (!verify) {
             b.verified = true;
@@ -446,25 +361,25 @@ struct hdfs3_block_reader {
         LaunchEnv env = launch_env(ctx, &b.a.pieces);
         env.tables = tables;
         env.fold = ctx->d_fold_by[tables == ctx->d_tables_by[1]];
-        HIP_OK(hipMemcpyAsync(b.a.d, b.a.h, b.used, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpyAsync(b.a.d, b.a.h, b.lay.used, hipMemcpyHostToDevice, ctx->stream));
         b.uploaded = true;
         HIP_OK(hipMemsetAsync(b.a.d_res, 0, sizeof(unsigned long long), ctx->stream));
-        if (b.dense) {
-            // one contiguous block of b.data_used bytes and its word array: the contiguous round kernel
+        if (b.lay.dense) {
+            // one contiguous block of data_used bytes and its word array: the contiguous round kernel
             // (bpc <= 4096), the multi-round kernel or pieces + combine (R x 4096, on the batch's own
             // piece scratch); keys are the batch's chunk indices (wait() maps them to packets)
             ChunkLaunch a{};
-            a.data = b.a.d + b.d0;
-            a.len = b.data_used;
+            a.data = b.a.d + b.lay.d0;
+            a.len = b.lay.data_used;
             a.bpc = chunk_size;
             a.crc_be = b.a.d;
             a.result = b.a.d_res;
             a.check_short_tail = 0;  // verifyChecksum ignores a short chunk's mismatch (:319)
             HIP_OK(launch_chunks(env, a, true));
         } else {
-            std::vector<DevPacket> hp(b.pk.size());
-            for (size_t i = 0; i < b.pk.size(); ++i)
-                hp[i] = DevPacket{b.pk[i].data_off, b.pk[i].crc_off, b.pk[i].data_len, 0};
+            const std::vector<PacketRef> &pk = b.lay.pk;
+            std::vector<DevPacket> hp(pk.size());
+            for (size_t i = 0; i < pk.size(); ++i) hp[i] = DevPacket{pk[i].data_off, pk[i].crc_off, pk[i].data_len, 0};
             HIP_OK(launch_packet_batch(env, b.a.d, hp.data(), hp.size(), chunk_size, true, /*check_short_tail=*/0,
                                        b.a.d_res, b.a.h_desc, b.a.d_desc));
         }
@@ -476,7 +391,7 @@ struct hdfs3_block_reader {
 
     // an arena for `b`: already owned, else one the ctx cached from an earlier reader, else new
     int acquire(Batch &b) {
-        Timer tm(t_ns[1]);
+        Timer tm(t_ns[kPhaseArena]);
 #if HDFS3_LAB
         if (prefetch && g_fail_prefetch_arenas.load() > 0 && g_fail_prefetch_arenas.fetch_sub(1) > 0) {
             t_hip_fault = true;
@@ -490,7 +405,7 @@ struct hdfs3_block_reader {
                 ctx->arena_cache.pop_back();
             }
         }
-        if (int rc = grow(b.a, std::max(b.a.cap, size_t(batch_packets) * kPacketGuess), size_t(batch_packets)))
+        if (int rc = grow(b.a, std::max(b.a.cap, ring_arena_bytes(batch_packets)), size_t(batch_packets)))
             return rx_fail(rc, "arena allocation failed");
         return 0;
     }
@@ -503,12 +418,12 @@ struct hdfs3_block_reader {
         struct CpuAdd {  // the thread's CPU time, whichever way the loop ends
             hdfs3_block_reader *r;
             uint64_t c0;
-            ~CpuAdd() { r->t_ns[7].fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed); }
+            ~CpuAdd() { r->t_ns[kPhaseReceiverCpu].fetch_add(thread_cpu_ns() - c0, std::memory_order_relaxed); }
         } cpu_add{this, cpu0};
         for (;;) {
             int s;
             {
-                Timer idle(t_ns[5]);
+                Timer idle(t_ns[kPhaseRxWaitFreeSlot]);
                 std::unique_lock<std::mutex> lk(mu);
                 cv.wait(lk, [&] { return stop || !free_slots.empty(); });
                 if (stop) break;
@@ -519,14 +434,14 @@ struct hdfs3_block_reader {
             t_hip_fault = false;
             int rc = acquire(b);
             if (!rc) rc = receive(b);
-            if (!rc && !b.pk.empty()) {
+            if (!rc && !b.lay.pk.empty()) {
                 rc = launch(b);
                 if (rc) recv_msg = hdfs3_crc_last_error();
             }
             if (rc && t_hip_fault) local_fault = true;
             {
                 std::lock_guard<std::mutex> lk(mu);
-                if (!rc && !b.pk.empty())
+                if (!rc && !b.lay.pk.empty())
                     ready.push_back(s);
                 else
                     free_slots.push_back(s);
@@ -545,7 +460,7 @@ struct hdfs3_block_reader {
 
     // ---- caller side ----------------------------------------------------------------------
     int wait_event(hipEvent_t ev) {
-        Timer tm(t_ns[3]);
+        Timer tm(t_ns[kPhaseGpuWait]);
         if (wait_mode == kWaitBlock) {
             HIP_OK(hipEventSynchronize(ev));  // a blocking-sync event (grow())
         } else {
@@ -562,13 +477,7 @@ struct hdfs3_block_reader {
     int wait(Batch &b) {
         if (b.verified) return 0;
         if (int rc = wait_event(b.a.done)) return rc;
-        const unsigned long long r = *b.a.h_res;
-        if (r && b.dense) {  // the first bad chunk of the batch -> its packet
-            const uint64_t chunk = ~r;
-            b.bad_pkt = int64_t(std::upper_bound(b.chunk0.begin(), b.chunk0.end(), chunk) - b.chunk0.begin()) - 1;
-        } else if (r) {
-            b.bad_pkt = int64_t((~r) >> 32);
-        }
+        if (const unsigned long long r = *b.a.h_res) b.bad_pkt = b.lay.bad_packet(r);
         b.verified = true;
         return 0;
     }
@@ -586,76 +495,67 @@ struct hdfs3_block_reader {
         if (net::write_delimited(fd, msg, timeout_ms) == 0) sent_status = true;
     }
 
+    // The batch to deliver from: *s is its slot, or -1 once the range is exhausted. The receiver's failure
+    // comes back (and stays, in error / error_msg) once the good batches before it were all delivered.
+    int front(int *s) {
+        Timer idle(t_ns[kPhaseCallerWaitBatch]);
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !ready.empty() || recv_done; });
+        *s = ready.empty() ? -1 : ready.front();
+        if (*s >= 0 || !recv_error) return 0;
+        error = recv_error;
+        error_msg = recv_msg;
+        return error;
+    }
+
+    // The front batch was delivered up to its limit: the ChecksumException when a bad packet set that
+    // limit, else the slot goes back to the receiver
+    int retire(int s) {
+        if (slot[s].bad_pkt >= 0)
+            return sticky(-EIO, "ChecksumException: RemoteBlockReader: checksum not match for Block: " +
+                                    std::to_string(block.block_id) + " (packet " + std::to_string(slot[s].bad_pkt) +
+                                    " of a GPU batch)");
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            ready.pop_front();
+            free_slots.push_back(s);
+        }
+        cv.notify_all();
+        return 0;
+    }
+
     int32_t read(uint8_t *out, int32_t len) {
         if (error) return fail(error, "%s", error_msg.c_str());
         if (len <= 0 || !out) return fail(-EINVAL, "invalid read buffer");
         int32_t total = 0;
         while (total < len) {
             int s;
-            {
-                Timer idle(t_ns[6]);
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !ready.empty() || recv_done; });
-                if (ready.empty()) {
-                    if (recv_error) {  // good batches were all delivered first
-                        const int code = recv_error;
-                        const std::string msg = recv_msg;
-                        lk.unlock();
-                        if (total) {
-                            error = code;
-                            error_msg = msg;
-                            return total;
-                        }
-                        return sticky(code, msg);
-                    }
-                    break;  // range exhausted
-                }
-                s = ready.front();
-            }
+            if (front(&s)) return total ? total : fail(error, "%s", error_msg.c_str());
+            if (s < 0) break;
             Batch &b = slot[s];
             if (int rc = wait(b)) {
                 local_fault = true;
                 return total ? total : sticky(rc, hdfs3_crc_last_error());
             }
-            const size_t limit = b.bad_pkt >= 0 ? size_t(b.bad_pkt) : b.pk.size();
+            const size_t limit = b.limit();
             {
-                Timer tm(t_ns[4]);
+                Timer tm(t_ns[kPhaseCopyOut]);
                 // (a copy per packet on this thread: splitting a call's copies over the copy
                 // pool gained nothing on a single TCP-bound stream and cost 8 concurrent
                 // streams ~20 %, profiles/r02/e2e_read_copy_pool_ab.jsonl)
-                while (total < len && b.dpkt < limit) {
-                    const PacketRef &p = b.pk[b.dpkt];
-                    const size_t avail = p.deliver - b.doff;
-                    const size_t n = std::min<size_t>(avail, size_t(len - total));
+                while (total < len && !b.cur.done(limit)) {
+                    const DeliveryCursor::Piece pc = b.cur.take(b.lay.pk, size_t(len - total));
                     if (dest && out + total == dest + delivered)
                         ;  // the receiver already put these bytes here
-                    else if (copy_nt && n >= 4096)
-                        memcpy_stream(out + total, b.a.h + p.data_off + p.skip + b.doff, n);
+                    else if (copy_nt && pc.n >= 4096)
+                        memcpy_stream(out + total, b.a.h + pc.src, pc.n);
                     else
-                        std::memcpy(out + total, b.a.h + p.data_off + p.skip + b.doff, n);
-                    total += int32_t(n);
-                    b.doff += n;
-                    delivered += int64_t(n);
-                    if (b.doff == p.deliver) {
-                        ++b.dpkt;
-                        b.doff = 0;
-                    }
+                        std::memcpy(out + total, b.a.h + pc.src, pc.n);
+                    total += int32_t(pc.n);
+                    delivered += int64_t(pc.n);
                 }
             }
-            if (b.dpkt == limit) {
-                if (b.bad_pkt >= 0) {
-                    sticky(-EIO, "ChecksumException: RemoteBlockReader: checksum not match for Block: " +
-                                     std::to_string(block.block_id) + " (packet " + std::to_string(b.bad_pkt) +
-                                     " of a GPU batch)");
-                    return total ? total : error;
-                }
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    ready.pop_front();
-                    free_slots.push_back(s);
-                }
-                cv.notify_all();
-            }
+            if (b.cur.done(limit) && retire(s)) return total ? total : error;
         }
         maybe_send_status();
         return total;
@@ -688,45 +588,30 @@ struct hdfs3_block_reader {
             enqueued = false;
             return 0;
         };
+        auto local_failure = [&](int rc) {  // a HIP failure on this thread ends the call and the reader
+            local_fault = true;
+            error = failed = rc;
+            error_msg = hdfs3_crc_last_error();
+        };
         while (total < len && !failed) {
             int s;
-            {
-                Timer idle(t_ns[6]);
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !ready.empty() || recv_done; });
-                if (ready.empty()) {
-                    if (recv_error) {  // good batches were all delivered first
-                        error = recv_error;
-                        error_msg = recv_msg;
-                        failed = error;
-                    }
-                    break;  // range exhausted
-                }
-                s = ready.front();
-            }
+            failed = front(&s);
+            if (failed || s < 0) break;
             Batch &b = slot[s];
             if (int rc = wait(b)) {
-                local_fault = true;
-                error = failed = rc;
-                error_msg = hdfs3_crc_last_error();
+                local_failure(rc);
                 break;
             }
-            const size_t limit = b.bad_pkt >= 0 ? size_t(b.bad_pkt) : b.pk.size();
+            const size_t limit = b.limit();
             {
-                Timer tm(t_ns[4]);
+                Timer tm(t_ns[kPhaseCopyOut]);
                 rg.clear();
                 const int32_t before = total;
-                while (total < len && b.dpkt < limit) {
-                    const PacketRef &p = b.pk[b.dpkt];
-                    const size_t n = std::min<size_t>(p.deliver - b.doff, size_t(len - total));
-                    rg.push_back(CopyRange{p.data_off + p.skip + b.doff, uint64_t(total), n});
-                    total += int32_t(n);
-                    b.doff += n;
-                    delivered += int64_t(n);
-                    if (b.doff == p.deliver) {
-                        ++b.dpkt;
-                        b.doff = 0;
-                    }
+                while (total < len && !b.cur.done(limit)) {
+                    const DeliveryCursor::Piece pc = b.cur.take(b.lay.pk, size_t(len - total));
+                    rg.push_back(CopyRange{pc.src, uint64_t(total), pc.n});
+                    total += int32_t(pc.n);
+                    delivered += int64_t(pc.n);
                 }
                 int rc = 0;
                 if (total > before) {
@@ -735,47 +620,30 @@ struct hdfs3_block_reader {
                     // against the upload: such a batch's copies are waited for before it goes back.
                     const bool own_upload = !b.uploaded;
                     if (own_upload) {
-                        const hipError_t e = hipMemcpyAsync(b.a.d, b.a.h, b.used, hipMemcpyHostToDevice, ctx->stream);
+                        const hipError_t e = hipMemcpyAsync(b.a.d, b.a.h, b.lay.used, hipMemcpyHostToDevice, ctx->stream);
                         if (e != hipSuccess) rc = hip_err(e, "hipMemcpyAsync");
                         b.uploaded = true;
                     }
                     unsigned launched = 0;
-                    if (!rc) rc = gather_dev(ctx, d_out, size_t(len), b.a.d, b.used, rg.data(), rg.size(), &launched);
+                    if (!rc) rc = gather_dev(ctx, d_out, size_t(len), b.a.d, b.lay.used, rg.data(), rg.size(), &launched);
                     enqueued = true;
                     if (!rc && own_upload) rc = complete();
                     dev_launches.fetch_add(launched, std::memory_order_relaxed);
                     dev_bytes.fetch_add(uint64_t(total - before), std::memory_order_relaxed);
                 }
                 if (rc) {
-                    local_fault = true;
-                    error = failed = rc;
-                    error_msg = hdfs3_crc_last_error();
+                    local_failure(rc);
                     break;
                 }
             }
-            if (b.dpkt == limit) {
-                if (b.bad_pkt >= 0) {
-                    failed = sticky(-EIO, "ChecksumException: RemoteBlockReader: checksum not match for Block: " +
-                                              std::to_string(block.block_id) + " (packet " + std::to_string(b.bad_pkt) +
-                                              " of a GPU batch)");
-                    break;
-                }
-                // the batch's gather is in the stream that carries this arena's next upload, which is
-                // thereby ordered behind it: the slot can go back now
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    ready.pop_front();
-                    free_slots.push_back(s);
-                }
-                cv.notify_all();
-            }
+            // (a good batch's gather is in the stream that carries this arena's next upload, which is
+            // thereby ordered behind it: the slot can go back now)
+            if (b.cur.done(limit)) failed = retire(s);
         }
         // the returned bytes are in place when the call returns: an event after the last gather, not a
         // drain of the stream (the receiver may have queued the next batch's upload and verify behind it)
         if (int rc = complete()) {
-            local_fault = true;
-            error = failed = rc;
-            error_msg = hdfs3_crc_last_error();
+            local_failure(rc);
             total = 0;  // nothing is known to be in place
         }
         if (failed) return total ? total : fail(error, "%s", error_msg.c_str());
@@ -786,12 +654,8 @@ struct hdfs3_block_reader {
     int64_t available() {
         std::lock_guard<std::mutex> lk(mu);
         int64_t a = 0;
-        for (int s : ready) {
-            const Batch &b = slot[s];
-            if (!b.verified) continue;
-            const size_t limit = b.bad_pkt >= 0 ? size_t(b.bad_pkt) : b.pk.size();
-            for (size_t i = b.dpkt; i < limit; ++i) a += b.pk[i].deliver - (i == b.dpkt ? b.doff : 0);
-        }
+        for (int s : ready)
+            if (slot[s].verified) a += slot[s].cur.remaining(slot[s].lay.pk, slot[s].limit());
         return a;
     }
 
@@ -835,13 +699,12 @@ bool block_reader_local_fault(const hdfs3_block_reader *r) { return r && r->loca
 
 int64_t block_reader_batch_bytes(const hdfs3_reader_opts *opts) {
     const int bp = opts && opts->batch_packets > 0 ? opts->batch_packets : kDefaultBatchPackets;
-    return int64_t(bp) * 64 * 1024;  // payload of a batch of 64 KiB datanode packets
+    return batch_payload_bytes(bp);
 }
 
 int64_t block_reader_arena_bytes(const hdfs3_reader_opts *opts) {
     const int bp = opts && opts->batch_packets > 0 ? opts->batch_packets : kDefaultBatchPackets;
-    // what acquire()/grow() pin for one batch: the arena, its descriptor staging and result word
-    return int64_t(bp) * int64_t(kPacketGuess + sizeof(DevSegment)) + int64_t(sizeof(unsigned long long));
+    return arena_pinned_bytes(bp);  // what acquire()/grow() pin for one batch
 }
 
 int open_block_reader(const char *host, int port, const hdfs3_block_id *blk, int64_t start, int64_t len,
@@ -964,7 +827,7 @@ void hdfs3x_fail_prefetch_arenas(int n) { g_fail_prefetch_arenas = n; }
 // measurement hook (libhdfs3_crc_lab.so only): nanoseconds spent per phase so far
 int hdfs3x_block_reader_timing(hdfs3_block_reader *r, uint64_t *out5) {
     if (!r || !out5) return fail(-EINVAL, "invalid argument");  // the first 5 phases
-    for (int i = 0; i < 5; ++i) out5[i] = r->t_ns[i].load();
+    for (int i = 0; i <= kPhaseCopyOut; ++i) out5[i] = r->t_ns[i].load();
     return 0;
 }
 #endif

@@ -27,15 +27,27 @@ GOOD = pkt(DATA.tobytes(), CRC, 0, 0)
 TRAILER = packet_header(4, 4096, 1, True, 0)
 
 
-def attempt(script, start=0, length=4096, received=None):
+def attempt(script, start=0, length=4096, received=None, batch_packets=64, info=None):
+    """Reads the range from the scripted datanode: (bytes, None) or (None, error). `info`, a dict, also
+    gets the reader's stats and the bytes delivered before the read ended either way."""
     from libhdfs3_amd.engine import BlockReader
     from libhdfs3_amd._native import Hdfs3CrcError
 
     port, t = serve_once(script, received)
     try:
-        with BlockReader("127.0.0.1", port, 1, start, length, timeout_ms=3000) as r:
-            out = r.read_all(length)
-        return out, None
+        with BlockReader("127.0.0.1", port, 1, start, length, timeout_ms=3000, batch_packets=batch_packets) as r:
+            out = np.empty(length, dtype=np.uint8)
+            pos = 0
+            try:
+                while pos < length:
+                    got = r.read_into(out, pos, length - pos)
+                    if got == 0:
+                        break
+                    pos += got
+            finally:
+                if info is not None:
+                    info.update(r.stats(), delivered=out[:pos].tobytes())
+        return out[:pos], None
     except Hdfs3CrcError as e:
         return None, e
     finally:
@@ -118,3 +130,28 @@ def test_any_positive_chunk_size(bpc):
         tail[-1] ^= 1
         out, err = attempt(lambda req: block_op_response(bpc=bpc) + pkt(DATA.tobytes(), bytes(tail), 0, 0) + TRAILER)
         assert err is None and out.tobytes() == DATA.tobytes()
+
+
+def test_partial_chunk_packet_mid_stream_seals_the_batch():
+    """A packet that ends in a partial chunk, mid-stream, ends the contiguous chunk run of a dense batch:
+    the batch is sealed after it and the next packet opens another (1,024 + 100 bytes, then 512). A flipped
+    bit in that next packet: the first batch's 1,124 bytes are delivered, then the ChecksumException."""
+    sizes, data = (1024, 100, 512), DATA.tobytes()[:1636]
+
+    def stream(payload):
+        out, off = block_op_response(), 0
+        for seq, n in enumerate(sizes):
+            out += pkt(payload[off:off + n], oracle_compute(DATA[off:off + n], 512).tobytes(), off, seq)
+            off += n
+        return out + packet_header(4, off, len(sizes), True, 0)
+
+    info = {}
+    out, err = attempt(lambda req: stream(data), length=1636, batch_packets=8, info=info)
+    assert err is None and out.tobytes() == data, err
+    assert info["gpu_batches"] == 2 and info["packets"] == 3, info
+    bad = bytearray(data)
+    bad[1124 + 300] ^= 0x10
+    info = {}
+    out, err = attempt(lambda req: stream(bytes(bad)), length=1636, batch_packets=8, info=info)
+    assert out is None and err is not None and err.rc == -5 and "ChecksumException" in str(err), err
+    assert info["delivered"] == data[:1124]
