@@ -195,6 +195,28 @@ typedef struct hdfs3_local_opts {
 int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_t num_bytes, int64_t offset,
                             const hdfs3_local_opts *opts, hdfs3_local_reader **out);
 int32_t hdfs3_local_reader_read(hdfs3_local_reader *r, void *buf, int32_t len);
+/* hdfs3_local_reader_read into DEVICE memory: same counts, 0 at the end of the block, the same errors. On
+ * a mismatch it returns the bytes before the buffer_size buffer that holds the first bad chunk and after
+ * that -EIO "ChecksumException" (the call that found the mismatch returns -EIO itself if it delivered
+ * nothing); the error is sticky. d_buf is device memory of the reader's device (opts->device), e.g. a
+ * torch tensor's data_ptr(); a host pointer or another device's memory gives -EINVAL and leaves the reader
+ * usable, len <= 0 or a null pointer gives -EINVAL. Each verified window is already in HBM (it was
+ * uploaded for its verify), so its bytes go from there to d_buf in one guarded delivery per window
+ * (hdfs3_deliver_verified_dev_async's kernel, granule = buffer_size) and no host copy-out or second
+ * upload is made. Unlike hdfs3_block_reader_read_dev the host does not read a window's verify result
+ * before the copy is enqueued: the kernel reads the result word itself and writes only what it allows, and
+ * the deliveries of one call are chained through two gate words, so a call that spans many windows
+ * enqueues verify -> delivery -> verify -> delivery on one stream and waits once, at its end, for the
+ * last gate word, which tells where the delivered bytes end. The reference's order, verify before copy
+ * (LocalBlockReader.cpp:138-163, 197-214), is kept on the device. The returned bytes are in place when the
+ * call returns, and no byte of d_buf past the returned count is written, at any time. With verify = 0 or a
+ * CHECKSUM_NULL block nothing was uploaded: the window's bytes go to d_buf with a runtime copy from the
+ * pinned window or the mapping, and no kernel runs. read and read_dev may be mixed on one reader; each
+ * continues at the cursor. A HIP failure on the calling thread ends the call and the reader; the call then
+ * returns the error, since nothing is known to be in place. */
+int32_t hdfs3_local_reader_read_dev(hdfs3_local_reader *r, void *d_buf, int32_t len);
+/* delivery launches made by read_dev so far and the bytes read_dev placed */
+int hdfs3_local_reader_device_stats(hdfs3_local_reader *r, uint64_t *deliver_launches, uint64_t *bytes_delivered);
 int64_t hdfs3_local_reader_available(hdfs3_local_reader *r);
 int hdfs3_local_reader_stats(hdfs3_local_reader *r, uint32_t *bytes_per_checksum, int *checksum_type,
                              uint64_t *gpu_batches);

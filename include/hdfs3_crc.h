@@ -307,6 +307,42 @@ typedef struct hdfs3_copy_range {
 } hdfs3_copy_range;
 int hdfs3_gather_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len,
                            const hdfs3_copy_range *ranges, size_t n);
+/* Guarded delivery: the gather behind a verify's result word, with the order "verify before copy" kept on
+ * the DEVICE. hdfs3_deliver_verified_dev_async copies the ranges exactly as hdfs3_gather_dev_async does
+ * (byte-exact, no alignment asked, partial lines byte by byte, nothing outside either buffer), but first
+ * the kernel itself reads two device words and clips every range to the LIMIT they give, a source offset:
+ *   *d_gate_in != 0                     -> 0: nothing is copied (an earlier delivery of the chain stopped);
+ *   *d_gate_in == 0, *d_result == 0     -> no limit;
+ *   *d_gate_in == 0, *d_result != 0     -> data_off + ((~*d_result) * bpc) / granule * granule: the whole
+ *                                          granule (counted from data_off) holding the bad chunk is withheld.
+ * d_result is the result word of the verify that covered the source data (0, or ~first_bad_chunk; chunk 0
+ * is the byte d_src + data_off); d_gate_in may be NULL (read as 0). A range {src_off, dst_off, len} copies
+ * its first clamp(limit - src_off, 0, len) bytes, so a range the limit cuts ends exactly at the limit.
+ * granule = bpc is chunk granularity; granule = the local buffer size is the short-circuit reader's rule.
+ * One lane writes *d_gate_out (may be NULL): *d_gate_in if that is non-zero, else ~(chunk_base +
+ * ~*d_result) if *d_result is non-zero, else 0 — the result words' encoding (hdfs3_crc_decode_result).
+ * d_gate_out must not be d_gate_in or d_result (other workgroups of the launch still read those), so a
+ * chain alternates between two gate words. With n == 0 the gate is still passed on.
+ *
+ * A caller can therefore enqueue verify -> delivery -> verify -> delivery on the ctx stream and wait once:
+ * the destination never holds a byte its verify did not pass, and after the first bad chunk nothing more
+ * is written. The call runs on the ctx stream and nothing waits; the guard words must be produced by work
+ * enqueued earlier on that stream, or be complete. More than 64 ranges take more launches, each reading
+ * the same words and writing the same value to *d_gate_out. -EINVAL (before any launch) for a null ctx or
+ * guard, a null d_result, granule == 0 or bpc == 0, d_gate_out equal to d_gate_in or d_result, a null
+ * buffer with n > 0, or a range outside src_len / dst_len. Like the gather it uses none of the ctx's
+ * staging (any thread may call it), and its launches count in hdfs3_crc_ctx_kernel_launches. */
+typedef struct hdfs3_deliver_guard {
+    const uint64_t *d_result;   /* device */
+    const uint64_t *d_gate_in;  /* device or NULL */
+    uint64_t *d_gate_out;       /* device or NULL */
+    uint64_t data_off;          /* offset in d_src of the verified data's chunk 0 */
+    uint64_t chunk_base;        /* added to the chunk index recorded in *d_gate_out */
+    uint64_t granule;           /* >= 1 */
+    uint32_t bpc;               /* >= 1 */
+} hdfs3_deliver_guard;
+int hdfs3_deliver_verified_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len,
+                                     const hdfs3_copy_range *ranges, size_t n, const hdfs3_deliver_guard *guard);
 /* Verify-then-deliver for callers with their own transport: verifies the packets exactly as
  * hdfs3_crc32c_verify_packets_dev (same bad_packet / bad_chunk), reads the result, and only then
  * gathers the data of every packet BEFORE the first bad one, back to back, to d_dst + dst_off (all

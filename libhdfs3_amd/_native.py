@@ -50,6 +50,13 @@ class CopyRange(ctypes.Structure):
     _fields_ = [("src_off", c_uint64), ("dst_off", c_uint64), ("len", c_uint64)]
 
 
+class DeliverGuard(ctypes.Structure):
+    """hdfs3_deliver_guard (include/hdfs3_crc.h)."""
+
+    _fields_ = [("d_result", c_void_p), ("d_gate_in", c_void_p), ("d_gate_out", c_void_p), ("data_off", c_uint64),
+                ("chunk_base", c_uint64), ("granule", c_uint64), ("bpc", c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol include/hdfs3_crc.h declares.
 PUBLIC_API = {
     "hdfs3_crc_abi_version": (c_int, []),
@@ -95,6 +102,8 @@ PUBLIC_API = {
     "hdfs3_crc32c_compute_packet_stream_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(PktStream),
                                                              c_uint32]),
     "hdfs3_gather_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(CopyRange), c_size_t]),
+    "hdfs3_deliver_verified_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(CopyRange),
+                                                 c_size_t, POINTER(DeliverGuard)]),
     "hdfs3_crc32c_verify_packets_gather_dev": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(PktDesc), c_size_t,
                                                        c_uint32, c_int, c_void_p, c_size_t, c_uint64,
                                                        POINTER(c_int64), POINTER(c_int64), POINTER(c_uint64)]),
@@ -242,6 +251,8 @@ CLIENT_API = {
     "hdfs3_local_reader_open": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_int64, c_int64, POINTER(LocalOpts),
                                         POINTER(c_void_p)]),
     "hdfs3_local_reader_read": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_local_reader_read_dev": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_local_reader_device_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "hdfs3_local_reader_available": (c_int64, [c_void_p]),
     "hdfs3_local_reader_stats": (c_int, [c_void_p, POINTER(c_uint32), POINTER(c_int), POINTER(c_uint64)]),
     "hdfs3_local_reader_mapped_windows": (c_uint64, [c_void_p]),

@@ -12,6 +12,9 @@
 // Delivery granularity on a mismatch is the reference's: readAndVerify verifies one
 // buffer_size buffer before any of it is returned, so bytes of the buffer holding the
 // first bad chunk — and everything after — are withheld and -EIO is returned.
+// read_dev() delivers into device memory instead: the window's device copy goes to the caller's
+// buffer in a guarded delivery (crc32c_gather.hip) that reads the window's result word on the
+// device, so the caller enqueues it without waiting for the verify (see read_dev_verified).
 //
 // Staging. Verification on: a window is pread into its pinned arena by the loader and the
 // helper threads together (a single pread thread was the single-stream limit), DMA'd, and
@@ -80,6 +83,21 @@ int hip_err(hipError_t e, const char *what) {
         if (e_ != hipSuccess) return hip_err(e_, #expr);  \
     } while (0)
 
+// read_dev's own words, made on a reader's first device read and pooled with the rest: the two gate words
+// of the delivery chain (device), the pinned word the last one is read back into, and the event behind it
+struct DeviceWords {
+    uint64_t *d_gate = nullptr;
+    unsigned long long *h_gate = nullptr;
+    hipEvent_t done = nullptr;
+
+    void release() {
+        if (d_gate) (void)hipFree(d_gate);
+        if (h_gate) (void)hipHostFree(h_gate);
+        if (done) (void)hipEventDestroy(done);
+        *this = DeviceWords();
+    }
+};
+
 // Reader resources — a ctx (stream, table images) and kSlots pinned + device windows —
 // are pooled per process. The reference opens one LocalBlockReader per block
 // (InputStreamImpl::setupBlockReader), and creating a ctx and pinning the windows costs
@@ -87,6 +105,7 @@ int hip_err(hipError_t e, const char *what) {
 struct LocalResources {
     hdfs3_crc_ctx *ctx = nullptr;
     PacketArena a[kSlots];
+    DeviceWords dev;
 };
 std::mutex g_pool_mu;
 std::vector<LocalResources> g_pool;
@@ -106,6 +125,7 @@ bool take_pooled(int device, size_t cap, LocalResources *out) {
 
 void free_resources(LocalResources &r) {
     for (PacketArena &a : r.a) a.release();
+    r.dev.release();
     ctx_release(r.ctx);
     r.ctx = nullptr;
 }
@@ -119,6 +139,8 @@ LocalPoolStats entry_bytes(const LocalResources &r) {
         st.pinned += n;
         st.device += n;
     }
+    if (r.dev.d_gate) st.device += 2 * sizeof(uint64_t);
+    if (r.dev.h_gate) st.pinned += sizeof(unsigned long long);
     st.entries = 1;
     return st;
 }
@@ -127,6 +149,7 @@ LocalPoolStats entry_bytes(const LocalResources &r) {
 // ctx into the ctx pool would only move the bytes the cap just refused into the other pool.
 void destroy_resources(LocalResources &r) {
     for (PacketArena &a : r.a) a.release();
+    r.dev.release();
     hdfs3_crc_ctx_destroy(r.ctx);
     r.ctx = nullptr;
 }
@@ -202,6 +225,7 @@ int local_pool_trim() {
     // destroyed outright, not released: a trim leaves no context behind in either pool
     for (LocalResources &e : idle) {
         for (PacketArena &a : e.a) a.release();
+        e.dev.release();
         hdfs3_crc_ctx_destroy(e.ctx);
     }
     return int(idle.size());
@@ -238,6 +262,11 @@ struct hdfs3_local_reader {
     size_t map_len = 0;                      // length rounded up to a page
     bool map_verified = false;               // HDFS3_LOCAL_MMAP=1: verified windows DMA'd from the mapping
     std::atomic<uint64_t> mapped_windows{0};
+    // read_dev
+    DeviceWords dev;
+    bool gate_zeroed = false;                // this reader's chain starts from two zero words
+    int gate_cur = 0;                        // the gate word the last delivery of the chain wrote
+    std::atomic<uint64_t> dev_launches{0}, dev_bytes{0};
 
     int sticky(int code, const std::string &msg) {
         error = code;
@@ -444,6 +473,241 @@ struct hdfs3_local_reader {
         return total;
     }
 
+    // ---- read() into device memory ----------------------------------------------------------
+    // Verification on: a window's bytes are already in HBM (load() uploaded them for the verify), so they go
+    // from w.a.d to d_out in one guarded delivery per window (deliver_dev: the kernel reads the window's result
+    // word itself and copies only what it allows). The caller's thread does not wait for a window's result
+    // before it enqueues: it waits for a window's `done` event only when it has nothing left to enqueue, to
+    // give the slot back (the loader's next pread overwrites the PINNED window, which no stream orders against
+    // the upload; the DEVICE copy needs no wait, the next upload into it is behind the delivery in the stream).
+    // The deliveries of one call form a chain over the reader's two gate words, so after a bad window nothing
+    // more is written, and the last gate word, read back once at the end, tells where the delivered bytes end.
+    int64_t good_end(int64_t bad_chunk) const {  // read()'s rule: up to the local buffer holding the bad chunk
+        const int64_t bad_off = bad_chunk * int64_t(chunk_size);
+        return first + (bad_off - first) / buffer_size * int64_t(buffer_size);
+    }
+
+    void give_slot_back(Window &w, int s) {
+        release_pages(w);  // its DMA completed: the `done` event has passed
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            ready.pop_front();
+            free_slots.push_back(s);
+        }
+        cv.notify_all();
+    }
+
+    int ensure_device_words() {
+        if (!dev.done) HIP_OK(hipEventCreateWithFlags(&dev.done, window_event_flags()));
+        if (!verify) return 0;
+        if (!dev.d_gate) HIP_OK(hipMalloc(reinterpret_cast<void **>(&dev.d_gate), 2 * sizeof(uint64_t)));
+        if (!dev.h_gate)
+            HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&dev.h_gate), sizeof(unsigned long long), pinned_host_flags()));
+        if (!gate_zeroed) {
+            HIP_OK(hipMemsetAsync(dev.d_gate, 0, 2 * sizeof(uint64_t), ctx->stream));
+            gate_zeroed = true;
+            gate_cur = 0;
+        }
+        return 0;
+    }
+
+    // an event behind everything this thread enqueued, waited for (not a drain: the loader may have queued
+    // the next window's upload and verify behind it)
+    int wait_enqueued() {
+        HIP_OK(hipEventRecord(dev.done, ctx->stream));
+        HIP_OK(hipEventSynchronize(dev.done));
+        return 0;
+    }
+
+    int32_t read_dev(uint8_t *d_out, int32_t len) {
+        if (error) return fail(error, "%s", error_msg.c_str());
+        if (!d_out || len <= 0) return fail(-EINVAL, "invalid read buffer");
+        DeviceGuard guard(ctx->device);
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, d_out) != hipSuccess || at.type != hipMemoryTypeDevice ||
+            at.device != ctx->device) {
+            (void)hipGetLastError();  // a host pointer is the caller's mistake, not a fault of the GPU
+            return fail(-EINVAL, "read_dev: the buffer is not device memory of device %d", ctx->device);
+        }
+        if (cursor >= length) return 0;
+        if (int rc = ensure_device_words()) return sticky(rc, std::string(hdfs3_crc_last_error()));
+        return verify ? read_dev_verified(d_out, len) : read_dev_plain(d_out, len);
+    }
+
+    // verify off or CHECKSUM_NULL: nothing was uploaded, so the window's bytes go from w.src (the pinned window
+    // or the mapping) to d_out with a runtime copy, waited for before the slot goes back. No kernel runs.
+    int32_t read_dev_plain(uint8_t *d_out, int32_t len) {
+        int32_t total = 0;
+        while (total < len && cursor < length) {
+            int s;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return !ready.empty() || load_done; });
+                if (ready.empty()) {
+                    if (load_error) {
+                        const int code = load_error;
+                        const std::string msg = load_msg;
+                        lk.unlock();
+                        if (total) {
+                            error = code;
+                            error_msg = msg;
+                            return total;
+                        }
+                        return sticky(code, msg);
+                    }
+                    break;
+                }
+                s = ready.front();
+            }
+            Window &w = slot[s];
+            const int64_t begin = std::max<int64_t>(cursor, w.start), end = w.start + w.len;
+            if (begin < end) {
+                const int64_t n = std::min<int64_t>(end - begin, len - total);
+                const hipError_t e =
+                    hipMemcpyAsync(d_out + total, w.src + (begin - w.start), size_t(n), hipMemcpyHostToDevice, ctx->stream);
+                int rc = e == hipSuccess ? 0 : hip_err(e, "hipMemcpyAsync");
+                if (!rc) rc = wait_enqueued();
+                if (rc) return sticky(rc, std::string(hdfs3_crc_last_error()));  // nothing is known to be in place
+                total += int32_t(n);
+                cursor = begin + n;
+                dev_bytes.fetch_add(uint64_t(n), std::memory_order_relaxed);
+            }
+            if (cursor >= end) give_slot_back(w, s);
+        }
+        return total;
+    }
+
+    int32_t read_dev_verified(uint8_t *d_out, int32_t len) {
+        const int64_t from = cursor;
+        int64_t pos = cursor;       // the enqueue cursor: deliveries for [from, pos) are in the stream
+        size_t held = 0;            // windows at the front of `ready` wholly enqueued, slots not yet given back
+        bool enqueued = false, chained = false, halt = false;
+        int64_t bad_chunk = -1;     // the first bad chunk (block-relative), once a bad window is known,
+        int64_t end = INT64_MAX;    // and where the deliverable bytes end before it
+        int load_code = 0;
+        std::string load_text;
+        // the front window was wholly enqueued: wait for its result; a good one's slot goes back to the loader
+        auto settle_front = [&]() -> int {
+            int s;
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                s = ready.front();
+            }
+            Window &w = slot[s];
+            if (int rc = wait(w)) return rc;
+            if (w.bad_chunk >= 0) {
+                halt = true;  // the deliveries behind it write nothing (the gate); nothing more is enqueued
+                return 0;
+            }
+            give_slot_back(w, s);
+            --held;
+            return 0;
+        };
+        while (!halt && pos - from < len && pos < length) {
+            int s = -1;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                if (held == 0) cv.wait(lk, [&] { return !ready.empty() || load_done; });
+                if (ready.size() > held) {
+                    s = ready[held];
+                } else if (held == 0) {
+                    load_code = load_error;
+                    load_text = load_msg;
+                }
+            }
+            if (s < 0) {
+                if (held == 0) break;  // the loader finished, or failed
+                // nothing left to enqueue: only now wait for the oldest window's event, for its slot
+                if (int rc = settle_front()) return sticky(rc, std::string(hdfs3_crc_last_error()));
+                continue;
+            }
+            Window &w = slot[s];
+            const int64_t begin = std::max<int64_t>(pos, w.start);
+            int64_t upto = w.start + w.len;
+            // a window an earlier call found bad stays at the front for the reader's life: the host knows where
+            // its good bytes end, and the delivery needs no gate (the chain's own stays closed)
+            const bool known_bad = w.verified && w.bad_chunk >= 0;
+            if (known_bad) {
+                bad_chunk = w.bad_chunk;
+                end = good_end(bad_chunk);
+                upto = std::min(upto, end);
+                halt = true;
+            }
+            const int64_t n = std::min<int64_t>(upto - begin, len - (begin - from));
+            if (n > 0) {
+                const CopyRange rg{uint64_t(begin - w.start), uint64_t(begin - from), uint64_t(n)};
+                const DeliverGuard g{reinterpret_cast<const uint64_t *>(w.a.d_res),
+                                     known_bad ? nullptr : dev.d_gate + gate_cur,
+                                     known_bad ? nullptr : dev.d_gate + (gate_cur ^ 1),
+                                     0,
+                                     uint64_t(w.start) / chunk_size,
+                                     uint64_t(buffer_size),
+                                     chunk_size};
+                unsigned launched = 0;
+                const int rc = deliver_dev(ctx, d_out, size_t(len), w.a.d, w.len, &rg, 1, g, &launched);
+                dev_launches.fetch_add(launched, std::memory_order_relaxed);
+                if (rc) return sticky(rc, std::string(hdfs3_crc_last_error()));  // nothing is known to be in place
+                enqueued = true;
+                if (!known_bad) {
+                    gate_cur ^= 1;
+                    chained = true;
+                }
+                pos = begin + n;
+            }
+            if (halt || pos < w.start + w.len) break;  // a window consumed in part stays at the front
+            ++held;
+        }
+        // the returned bytes are in place when the call returns: the chain's last gate word comes back behind
+        // the last delivery, and says whether, and at which chunk, the chain stopped
+        if (enqueued) {
+            int rc = 0;
+            if (chained) {
+                const hipError_t e = hipMemcpyAsync(dev.h_gate, dev.d_gate + gate_cur, sizeof(unsigned long long),
+                                                    hipMemcpyDeviceToHost, ctx->stream);
+                if (e != hipSuccess) rc = hip_err(e, "hipMemcpyAsync");
+            }
+            if (!rc) rc = wait_enqueued();
+            if (rc) return sticky(rc, std::string(hdfs3_crc_last_error()));
+            if (chained && *dev.h_gate) {
+                bad_chunk = hdfs3_crc_decode_result(*dev.h_gate);
+                end = good_end(bad_chunk);
+            }
+        }
+        const int64_t reached = std::min(pos, std::max(end, from));
+        const int32_t total = int32_t(reached - from);
+        cursor = reached;
+        dev_bytes.fetch_add(uint64_t(total), std::memory_order_relaxed);
+        // every window a delivery was enqueued from has passed its event by now: the good ones this call
+        // consumed go back, a bad one stays (and everything behind it)
+        for (;;) {
+            int s;
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                if (ready.empty()) break;
+                s = ready.front();
+            }
+            Window &w = slot[s];
+            if (w.start >= pos) break;  // not touched
+            if (int rc = wait(w)) return sticky(rc, std::string(hdfs3_crc_last_error()));
+            if (w.bad_chunk >= 0 || cursor < w.start + w.len) break;
+            give_slot_back(w, s);
+        }
+        if (bad_chunk >= 0 && cursor >= end) {
+            sticky(-EIO, "ChecksumException: LocalBlockReader checksum not match for block (chunk " +
+                             std::to_string(bad_chunk) + ")");
+            return total ? total : error;
+        }
+        if (load_code) {
+            if (total) {
+                error = load_code;
+                error_msg = load_text;
+                return total;
+            }
+            return sticky(load_code, load_text);
+        }
+        return total;
+    }
+
     int64_t available() {
         std::lock_guard<std::mutex> lk(mu);
         int64_t a = 0;
@@ -466,6 +730,7 @@ struct hdfs3_local_reader {
             LocalResources res;
             res.ctx = ctx;
             for (int i = 0; i < kSlots; ++i) res.a[i] = slot[i].a;
+            res.dev = dev;
             // a ctx whose stream completes cleanly goes back to the pool for the next reader
             const bool clean = hipStreamSynchronize(ctx->stream) == hipSuccess;
             for (Window &w : slot) release_pages(w);  // no DMA is in flight any more
@@ -544,6 +809,7 @@ int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_
     if (take_pooled(device, r->cap_data + crc_bytes, &pooled)) {
         r->ctx = pooled.ctx;
         for (int i = 0; i < kSlots; ++i) r->slot[i].a = pooled.a[i];
+        r->dev = pooled.dev;
     } else {
         if (int rc = ctx_acquire(device, &r->ctx)) return bail(rc);
         // the windows are pinned from a thread bound to the GPU's NUMA node (numa.h), so the
@@ -594,6 +860,18 @@ int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_
 int32_t hdfs3_local_reader_read(hdfs3_local_reader *r, void *buf, int32_t len) {
     if (!r) return fail(-EINVAL, "null reader");
     return r->read(static_cast<uint8_t *>(buf), len);
+}
+
+int32_t hdfs3_local_reader_read_dev(hdfs3_local_reader *r, void *d_buf, int32_t len) {
+    if (!r) return fail(-EINVAL, "null reader");
+    return r->read_dev(static_cast<uint8_t *>(d_buf), len);
+}
+
+int hdfs3_local_reader_device_stats(hdfs3_local_reader *r, uint64_t *deliver_launches, uint64_t *bytes_delivered) {
+    if (!r) return fail(-EINVAL, "null reader");
+    if (deliver_launches) *deliver_launches = r->dev_launches.load();
+    if (bytes_delivered) *bytes_delivered = r->dev_bytes.load();
+    return 0;
 }
 
 int64_t hdfs3_local_reader_available(hdfs3_local_reader *r) { return r ? r->available() : 0; }

@@ -18,6 +18,12 @@
 // (the first and last quad of a buffer whose ends are not 16-byte aligned) the line's bytes are loaded
 // one by one, each tested against the buffer. A buffer resource's range check cannot serve here: it
 // drops a 16-byte load whole when its last byte is out of range, and the bytes before it are needed.
+//
+// The guarded delivery (the kernel's second instantiation) is the same copy behind a verify's result
+// word: it reads that word and a chain word on the device, clips every range to the limit they give
+// (launch_plan.h: deliver_limit) and leaves the chain word for the next delivery, so verify -> copy ->
+// verify -> copy can sit on one stream with no host read in between and the destination still never
+// holds an unverified byte.
 #include <hip/hip_runtime.h>
 
 #include "crc32c_kernels.h"
@@ -46,8 +52,28 @@ __device__ __forceinline__ u32x4g shift_quads(const u32x4g lo, const u32x4g hi, 
     return o;
 }
 
+// One kernel, two instantiations. Without a guard argument (launch_gather) it is the plain gather. With one
+// (launch_deliver: Guard = DeliverGuard) it is the guarded delivery, the same copy behind a verify's result
+// word: every workgroup reads the two guard words itself (uniform loads, once) and derives the limit, a source
+// offset at which every range ends, so the copy is ordered behind the verify on the device and the host never
+// reads the result in between. One lane of the launch leaves the chain word for the next delivery; gate_out
+// aliases neither word read here (checked by the host), since other workgroups of the launch may still be
+// reading them. A delivery with g.n == 0 only passes the gate on.
+template <typename... Guard>
 __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *dst, uint64_t dst_len, const uint8_t *src,
-                                                                       uint64_t src_len, const GatherLaunch g) {
+                                                                       uint64_t src_len, const GatherLaunch g,
+                                                                       const Guard... guard) {
+    constexpr bool kGuarded = sizeof...(Guard) != 0;
+    uint64_t limit = kDeliverNoLimit;
+    if constexpr (kGuarded) {
+        const DeliverGuard &gd = (guard, ...);
+        const uint64_t result = *gd.result;
+        const uint64_t gate_in = gd.gate_in ? *gd.gate_in : 0;
+        if (blockIdx.x == 0 && threadIdx.x == 0 && gd.gate_out) *gd.gate_out = deliver_gate(result, gate_in, gd.chunk_base);
+        if (g.n == 0) return;
+        limit = deliver_limit(result, gate_in, gd.data_off, gd.granule, gd.bpc);
+        if (limit == 0) return;
+    }
     // the workgroup's range: the first whose tile_end is above this tile
     const uint32_t tile = blockIdx.x;
     uint32_t lo_r = 0, hi_r = g.n - 1;
@@ -59,7 +85,12 @@ __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *
     const uint32_t r = lo_r;
     if (tile >= g.tile_end[r]) return;  // a grid larger than the plan
     const uint32_t ltile = tile - (r ? g.tile_end[r - 1] : 0);
-    const CopyRange c = g.r[r];
+    CopyRange c = g.r[r];
+    if constexpr (kGuarded) {
+        // a range the limit cuts ends exactly there: its last line becomes a partial one
+        c.len = deliver_clip(limit, c.src_off, c.len);
+        if (c.len == 0) return;
+    }
 
     const uint64_t src_b = reinterpret_cast<uint64_t>(src), src_e = src_b + src_len;
     const uint64_t dst_b = reinterpret_cast<uint64_t>(dst), dst_e = dst_b + dst_len;
@@ -106,11 +137,19 @@ __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *
 
 }  // namespace
 
+hipError_t launch_deliver(hipStream_t stream, void *d_dst, uint64_t dst_len, const void *d_src, uint64_t src_len,
+                          const GatherLaunch &g, const DeliverGuard &guard) {
+    if (g.n > kGatherMaxRanges) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_ranges_kernel<DeliverGuard>, dim3(g.n ? g.tile_end[g.n - 1] : 1), dim3(kGatherThreads), 0, stream,
+                       static_cast<uint8_t *>(d_dst), dst_len, static_cast<const uint8_t *>(d_src), src_len, g, guard);
+    return hipGetLastError();
+}
+
 hipError_t launch_gather(hipStream_t stream, void *d_dst, uint64_t dst_len, const void *d_src, uint64_t src_len,
                          const GatherLaunch &g) {
     if (g.n == 0) return hipSuccess;
     if (g.n > kGatherMaxRanges) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gather_ranges_kernel, dim3(g.tile_end[g.n - 1]), dim3(kGatherThreads), 0, stream,
+    hipLaunchKernelGGL(gather_ranges_kernel<>, dim3(g.tile_end[g.n - 1]), dim3(kGatherThreads), 0, stream,
                        static_cast<uint8_t *>(d_dst), dst_len, static_cast<const uint8_t *>(d_src), src_len, g);
     return hipGetLastError();
 }

@@ -181,6 +181,11 @@ hipError_t launch_compose_words(const LaunchEnv &env, ComposeScratch *scratch, c
 // staging buffer is involved (any thread may launch on `stream`). g.n == 0 launches nothing.
 hipError_t launch_gather(hipStream_t stream, void *d_dst, uint64_t dst_len, const void *d_src, uint64_t src_len,
                          const GatherLaunch &g);
+// The same launch as a guarded delivery (launch_plan.h: DeliverGuard): every range clipped on the device to
+// the limit the guard's words give, *guard.gate_out written by one lane. g.n == 0 launches one workgroup
+// that only passes the gate on.
+hipError_t launch_deliver(hipStream_t stream, void *d_dst, uint64_t dst_len, const void *d_src, uint64_t src_len,
+                          const GatherLaunch &g, const DeliverGuard &guard);
 
 // HDFS3_LAB=1 builds the measurement library (libhdfs3_crc_lab.so: tools/, the A/B tests):
 // the same production launchers plus a process-wide kernel-variant knob, the kernel

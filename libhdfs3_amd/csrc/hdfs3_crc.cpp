@@ -759,6 +759,35 @@ int gather_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_sr
     }
     return 0;
 }
+
+int deliver_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len, const CopyRange *r,
+                size_t n, const DeliverGuard &guard, unsigned *launched) {
+    if (!guard.result) return fail(-EINVAL, "null result word");
+    if (guard.granule == 0 || guard.bpc == 0) return fail(-EINVAL, "granule and bpc must be at least 1");
+    if (guard.gate_out && (guard.gate_out == guard.gate_in || guard.gate_out == guard.result))
+        return fail(-EINVAL, "gate_out aliases a word the same launch reads");
+    const size_t bad = gather_first_bad(r, n, src_len, dst_len);
+    if (bad != n)
+        return fail(-EINVAL, "range %zu lies outside the %zu-byte source or the %zu-byte destination", bad, src_len,
+                    dst_len);
+    GatherLaunch g;
+    bool any = false;
+    for (size_t pos = 0; pos < n;) {
+        pos = plan_gather_launch(reinterpret_cast<uintptr_t>(d_dst), r, n, pos, &g);
+        if (g.n == 0) continue;  // nothing but empty ranges
+        HIP_TRY(launch_deliver(ctx->stream, d_dst, dst_len, d_src, src_len, g, guard));
+        any = true;
+        ++ctx->launches;
+        if (launched) ++*launched;
+    }
+    if (!any && guard.gate_out) {  // nothing to copy: the chain word is still passed on
+        g.n = 0;
+        HIP_TRY(launch_deliver(ctx->stream, d_dst, dst_len, d_src, src_len, g, guard));
+        ++ctx->launches;
+        if (launched) ++*launched;
+    }
+    return 0;
+}
 }  // namespace hdfs3crc
 
 extern "C" {
@@ -1001,6 +1030,17 @@ int hdfs3_gather_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, cons
     if (!d_dst || !d_src || !ranges) return fail(-EINVAL, "null buffer");
     DeviceGuard g(ctx->device);
     return gather_dev(ctx, d_dst, dst_len, d_src, src_len, reinterpret_cast<const CopyRange *>(ranges), n);
+}
+
+int hdfs3_deliver_verified_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len,
+                                     const hdfs3_copy_range *ranges, size_t n, const hdfs3_deliver_guard *guard) {
+    if (!ctx) return fail(-EINVAL, "null hdfs3_crc_ctx");
+    if (!guard) return fail(-EINVAL, "null guard");
+    if (n && (!d_dst || !d_src || !ranges)) return fail(-EINVAL, "null buffer");
+    const DeliverGuard dg{guard->d_result, guard->d_gate_in, guard->d_gate_out, guard->data_off,
+                          guard->chunk_base, guard->granule,   guard->bpc};
+    DeviceGuard g(ctx->device);
+    return deliver_dev(ctx, d_dst, dst_len, d_src, src_len, reinterpret_cast<const CopyRange *>(ranges), n, dg);
 }
 
 int hdfs3_crc32c_verify_packets_gather_dev(hdfs3_crc_ctx *ctx, const void *d_arena, size_t arena_len,

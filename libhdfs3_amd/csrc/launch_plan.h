@@ -153,4 +153,40 @@ size_t gather_first_bad(const CopyRange *in, size_t n, uint64_t src_len, uint64_
 // but empty ranges were left). The ranges were checked by gather_first_bad.
 size_t plan_gather_launch(uint64_t dst_addr, const CopyRange *in, size_t n, size_t pos, GatherLaunch *g);
 
+// ---- guarded delivery (crc32c_gather.hip: the gather behind a verify's result word) -----------------
+// A delivery copies ranges as the gather does, each clipped to a LIMIT (a source offset) that the kernel
+// derives from two device words: the result word of the verify that covered the source data (0, or
+// ~first_bad_chunk; chunk 0 is the source byte data_off) and a chain word gate_in (non-zero: an earlier
+// delivery of the chain stopped, nothing is copied). The kernel and the host (which needs the same number
+// to know how many bytes arrived) share the arithmetic below.
+constexpr uint64_t kDeliverNoLimit = ~uint64_t(0);
+// The limit: 0 behind a closed gate, none behind a clean result, else the start of the granule (counted
+// from data_off) that holds the bad chunk. granule, bpc >= 1. Saturates instead of wrapping: a bad chunk
+// whose offset does not fit 64 bits lies past every buffer, as no limit does.
+constexpr uint64_t deliver_limit(uint64_t result, uint64_t gate_in, uint64_t data_off, uint64_t granule, uint32_t bpc) {
+    if (gate_in) return 0;
+    if (!result) return kDeliverNoLimit;
+    const uint64_t bad = ~result;
+    if (bad > kDeliverNoLimit / bpc) return kDeliverNoLimit;
+    const uint64_t off = bad * bpc / granule * granule;
+    return off > kDeliverNoLimit - data_off ? kDeliverNoLimit : data_off + off;
+}
+// bytes of a range {src_off, len} below the limit: its first clamp(limit - src_off, 0, len)
+constexpr uint64_t deliver_clip(uint64_t limit, uint64_t src_off, uint64_t len) {
+    return limit <= src_off ? 0 : limit - src_off < len ? limit - src_off : len;
+}
+// The chain word a delivery leaves: a closed gate stays as it is, a bad result closes it with the bad
+// chunk's index plus chunk_base in the result words' own encoding, a clean one leaves it open (0)
+constexpr uint64_t deliver_gate(uint64_t result, uint64_t gate_in, uint64_t chunk_base) {
+    return gate_in ? gate_in : result ? ~(chunk_base + ~result) : 0;
+}
+// The guard as the kernel receives it (mirrors hdfs3_deliver_guard)
+struct DeliverGuard {
+    const uint64_t *result;
+    const uint64_t *gate_in;  // may be null: read as 0
+    uint64_t *gate_out;       // may be null
+    uint64_t data_off, chunk_base, granule;
+    uint32_t bpc;
+};
+
 }  // namespace hdfs3crc

@@ -285,6 +285,16 @@ class CrcContext:
               self._lib.hdfs3_gather_dev_async(self.ctx, d_dst, dst_len, d_src, src_len, self._ranges(ranges),
                                                len(ranges)))
 
+    def deliver_verified_dev(self, d_dst: int, dst_len: int, d_src: int, src_len: int, ranges, *, d_result: int,
+                             bpc: int, granule: int, data_off: int = 0, chunk_base: int = 0,
+                             d_gate_in: int | None = None, d_gate_out: int | None = None) -> None:
+        """hdfs3_deliver_verified_dev_async: the gather clipped on the device to what the verify result word
+        d_result (and the chain word d_gate_in) allow; enqueued on the ctx stream."""
+        guard = _native.DeliverGuard(d_result, d_gate_in, d_gate_out, data_off, chunk_base, granule, bpc)
+        self._check("hdfs3_deliver_verified_dev_async",
+              self._lib.hdfs3_deliver_verified_dev_async(self.ctx, d_dst, dst_len, d_src, src_len,
+                                                         self._ranges(ranges), len(ranges), byref(guard)))
+
     def verify_packets_gather_dev(self, d_arena: int, arena_len: int, pk, bpc: int, d_dst: int, dst_len: int,
                                   dst_off: int = 0, check_short_tail: bool = False):
         """hdfs3_crc32c_verify_packets_gather_dev: (bad_packet, bad_chunk, delivered)."""
@@ -756,6 +766,18 @@ class LocalBlockReader:
                 break
             pos += got
         return out[:pos]
+
+    def read_into_device(self, d_buf: int, n: int) -> int:
+        """hdfs3_local_reader_read_dev: up to n verified bytes to the device address d_buf (memory of the
+        reader's device, e.g. a torch tensor's data_ptr()); returns bytes (0 = end of block)."""
+        got = self._lib.hdfs3_local_reader_read_dev(self.r, d_buf, min(n, 0x7FFFFFFF))
+        return check("hdfs3_local_reader_read_dev", got)
+
+    def device_stats(self):
+        launches, placed = ctypes.c_uint64(), ctypes.c_uint64()
+        check("hdfs3_local_reader_device_stats",
+              self._lib.hdfs3_local_reader_device_stats(self.r, byref(launches), byref(placed)))
+        return {"deliver_launches": launches.value, "bytes_delivered": placed.value}
 
     def stats(self):
         from ctypes import c_uint32, c_uint64
