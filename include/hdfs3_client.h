@@ -91,7 +91,8 @@ int hdfs3_reader_phase_ns(uint64_t *out, int n, int reset);
  * Input stream: the hdfsRead / hdfsPread / hdfsSeek / hdfsTell / hdfsAvailable surface
  * (Hdfs.cpp:788-862, 924-941) over InputStreamImpl's block walk and replica failover
  * (InputStreamImpl.cpp:322-450, 583-815, 1120-1160), reading every block through
- * hdfs3_block_reader. The namenode lookup (getBlockLocations) is outside the checksum
+ * hdfs3_block_reader, or through hdfs3_local_reader where the caller registered a local
+ * replica (hdfs3_input_set_local_replicas, below). The namenode lookup (getBlockLocations) is outside the checksum
  * path: the caller passes the LocatedBlocks it would have received.
  *
  * Error convention of these five calls is hdfs.h's, not the -errno of the rest of this
@@ -225,6 +226,61 @@ int hdfs3_local_reader_stats(hdfs3_local_reader *r, uint32_t *bytes_per_checksum
  * HDFS3_LOCAL_MMAP=0 disables it). The others were staged by pread into pinned windows. */
 uint64_t hdfs3_local_reader_mapped_windows(hdfs3_local_reader *r);
 int hdfs3_local_reader_close(hdfs3_local_reader *r);
+
+/* ---- short-circuit replicas inside hdfs3_input_stream -------------------------------------
+ * InputStreamImpl::setupBlockReader builds a LocalBlockReader when the chosen node is local and
+ * short-circuit reads are on (InputStreamImpl.cpp:392-416). Here the caller says which replicas are
+ * local: registration IS the locality decision, and an entry is what
+ * ReadShortCircuitInfoBuilder::fetchOrCreate would return for the replica (the fd-passing and
+ * domain-socket plumbing is out of scope: the caller names the files). */
+typedef struct hdfs3_local_replica {
+    int block;              /* index into the blocks[] the stream was opened with */
+    int replica;            /* index into blocks[block].replicas                   */
+    const char *data_path;  /* the block file                                      */
+    const char *meta_path;  /* its .meta                                           */
+} hdfs3_local_replica;
+
+/* Replaces the stream's table of local replicas (n = 0 clears it: the stream then reads every block
+ * through hdfs3_block_reader, as one that never had a table); paths are copied. lopts gives buffer_size,
+ * window_buffers and flags of the local readers (NULL: their defaults); lopts->device and lopts->verify
+ * are ignored, the stream's own opts decide both. Takes effect at the next reader set-up; a reader that
+ * is open stays open. 0, or -EINVAL with the table unchanged: a block or replica index out of range, a
+ * null path, the same (block, replica) twice, unknown flags, buffer_size above 1 GiB.
+ *
+ * With a table, whenever the node chosen for a block (the first replica not yet failed) has a registered,
+ * still-valid entry, read / read_dev / pread / pread_dev read that block through hdfs3_local_reader
+ * (read_dev: its guarded delivery straight into d_buf) with the same counts, cursor rules, end of file
+ * and -1 + errno as before:
+ *  - a local reader that cannot be opened (missing file, bad meta version, unknown checksum type, bad
+ *    checksum parameter, offset beyond the file) or that fails while reading (ChecksumException, a file
+ *    error, a block file shorter than the block) makes the entry invalid for the rest of the stream's
+ *    life, and the SAME node is read through the remote reader from the cursor on (pread: the range again
+ *    from its first byte). The node does not go on the failed list (temporaryDisableLocalRead, :690-706);
+ *    if that remote reader fails too, the usual failover follows. Bytes the local reader returned before
+ *    it failed stay delivered: they were verified, under the local rule (nothing of the buffer_size buffer
+ *    holding the bad chunk);
+ *  - a fault of this host (a HIP error, -ENOMEM, -ENODEV, -ENOTSUP) is reported and neither invalidates
+ *    the entry nor fails the node; a destination that is not the device's memory is -1 / EINVAL likewise;
+ *  - pread opens a local reader for the range: whole buffer_size buffers are verified, counted from the
+ *    chunk-aligned first byte read, up to the end of the buffer holding the range's last byte (clipped to
+ *    the block), as LocalBlockReader's refills are (LocalBlockReader.cpp:201-206); nothing beyond is read;
+ *  - seek: a forward seek of <= 128 KiB inside the block skips through the open local reader by reading and
+ *    discarding, so the buffers skipped over ARE verified, which the reference's LocalBlockReader::skip
+ *    (:233-280) does not do; a bad one abandons the entry, and the read at the target goes to the same
+ *    node's remote reader. Any other seek reopens;
+ *  - block read-ahead skips a block whose first replica has a valid entry (the local reader's loader thread
+ *    reads ahead itself);
+ *  - verify = 0: the local reader runs unverified, as the reference's does; no data can cause a fallback.
+ * The local reader checks a short last chunk and the remote reader ignores its mismatch
+ * (RemoteBlockReader.cpp:319), so a block whose .meta has only its last word wrong falls back and is then
+ * served by the remote reader: the reference's behaviour too. */
+int hdfs3_input_set_local_replicas(hdfs3_input_stream *s, const hdfs3_local_replica *local, int n,
+                                   const hdfs3_local_opts *lopts);
+/* local readers opened, times a local replica was abandoned for the same node's remote reader, and bytes
+ * handed to the caller from local readers; all 0 on a stream with no table. hdfs3_input_stats keeps its
+ * meaning: readers_opened counts remote block readers, failovers the nodes put on the failed list. */
+int hdfs3_input_local_stats(hdfs3_input_stream *s, uint64_t *local_readers_opened,
+                            uint64_t *local_fallbacks, uint64_t *local_bytes);
 
 /* ------------------------------------------------------------------------------------
  * Output stream: the hdfsWrite / hdfsFlush / hdfsSync / hdfsTell / hdfsCloseFile surface

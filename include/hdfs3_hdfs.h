@@ -107,6 +107,19 @@ int hdfs3_fs_set_append_stamp(hdfsFS fs, const char *path, uint64_t new_generati
  * hdfs3_client.h; 0 blocks = off, the reference's one-block-at-a-time reading; at most
  * HDFS3_READAHEAD_MAX_BLOCKS). 0, or -1 with errno (EINVAL). */
 int hdfs3_fs_set_readahead(hdfsFS fs, int blocks, int64_t max_bytes_per_block);
+/* Short-circuit reads (hdfs3_input_set_local_replicas in hdfs3_client.h). add_local_replica says that
+ * replica `replica` of block `block` of `path` is on this machine, in data_path with its checksums in
+ * meta_path (copied): what ReadShortCircuitInfoBuilder::fetchOrCreate would return. Files opened for
+ * reading afterwards read that block from those files, and fall back to the same datanode when they
+ * cannot. 0, or -1 with errno: ENOENT for a path with no registered located blocks, EINVAL for an index
+ * out of range, a null or empty path, or a (block, replica) already added. hdfs3_fs_add_file on an
+ * existing path replaces the entry and so drops its local replicas. */
+int hdfs3_fs_add_local_replica(hdfsFS fs, const char *path, int block, int replica,
+                               const char *data_path, const char *meta_path);
+/* dfs.client.read.shortcircuit for files opened from now on (default on; off: registered local
+ * replicas are ignored), and the local readers' buffer_size, window_buffers and flags (NULL: their
+ * defaults). 0, or -1 with errno (EINVAL: unknown flags, buffer_size above 1 GiB). */
+int hdfs3_fs_set_local_read(hdfsFS fs, int on, const hdfs3_local_opts *lopts);
 /* hdfsRead / hdfsPread with the destination in DEVICE memory (hdfs3_input_read_dev / _pread_dev in
  * hdfs3_client.h): d_buffer is memory of the GPU the fs's read_opts name, e.g. a torch tensor's
  * data_ptr(). Same counts, cursor rules, failover and -1 + errno as hdfsRead / hdfsPread; the bytes

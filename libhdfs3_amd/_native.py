@@ -177,6 +177,12 @@ class LocalOpts(ctypes.Structure):
                 ("flags", c_uint32)]
 
 
+class LocalReplica(ctypes.Structure):
+    """hdfs3_local_replica (include/hdfs3_client.h)."""
+
+    _fields_ = [("block", c_int), ("replica", c_int), ("data_path", ctypes.c_char_p), ("meta_path", ctypes.c_char_p)]
+
+
 class PacketInfo(ctypes.Structure):
     """hdfs3_packet_info (include/hdfs3_client.h)."""
 
@@ -248,6 +254,8 @@ CLIENT_API = {
     "hdfs3_input_close": (c_int, [c_void_p]),
     "hdfs3_input_set_readahead": (c_int, [c_void_p, c_int, c_int64]),
     "hdfs3_input_readahead_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    "hdfs3_input_set_local_replicas": (c_int, [c_void_p, POINTER(LocalReplica), c_int, POINTER(LocalOpts)]),
+    "hdfs3_input_local_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
     "hdfs3_local_reader_open": (c_int, [ctypes.c_char_p, ctypes.c_char_p, c_int64, c_int64, POINTER(LocalOpts),
                                         POINTER(c_void_p)]),
     "hdfs3_local_reader_read": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
@@ -306,6 +314,9 @@ HDFS_API = {
     "hdfs3_fs_set_sink": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_void_p]),
     "hdfs3_fs_set_pipeline": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_int]),
     "hdfs3_fs_set_readahead": (c_int, [c_void_p, c_int, c_int64]),
+    "hdfs3_fs_add_local_replica": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_int, ctypes.c_char_p,
+                                           ctypes.c_char_p]),
+    "hdfs3_fs_set_local_read": (c_int, [c_void_p, c_int, POINTER(LocalOpts)]),
     "hdfs3_fs_read_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32]),
     "hdfs3_fs_pread_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32, c_int64]),
     "hdfs3_fs_write_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32]),

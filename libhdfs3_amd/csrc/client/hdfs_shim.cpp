@@ -78,9 +78,16 @@ struct BlockTable {
     }
 };
 
+// hdfs3_fs_add_local_replica: a replica of one of the file's blocks that is on this machine
+struct LocalFiles {
+    int block, replica;
+    std::string data, meta;
+};
+
 struct FileEntry {
     BlockTable located_blocks;
     bool located = false;  // registered by hdfs3_fs_add_file (a file of 0 blocks is empty)
+    std::vector<LocalFiles> local;  // dropped whenever located_blocks is replaced
     hdfs3_packet_sink sink = nullptr;
     void *user = nullptr;
     BlockTable pipeline_blocks;  // hdfs3_fs_set_pipeline: the blocks addBlock would allocate
@@ -99,6 +106,8 @@ struct HdfsFileSystemInternalWrapper {
     hdfs3_writer_opts wopts{0, 512, 65536, int64_t(128) << 20, 64};
     int readahead_blocks = 0;         // hdfs3_fs_set_readahead: for files opened for reading
     int64_t readahead_bytes = 0;
+    bool local_read = true;           // hdfs3_fs_set_local_read (dfs.client.read.shortcircuit)
+    hdfs3_local_opts lopts{0, 1, 0, 0, 0};  // buffer_size, window_buffers, flags of the local readers
     std::mutex mu;
     std::map<std::string, FileEntry> files;
 };
@@ -155,6 +164,34 @@ int hdfs3_fs_add_file(hdfsFS fs, const char *path, const hdfs3_located_block *bl
     FileEntry &slot = fs->files[path];
     slot.located_blocks = t;
     slot.located = true;
+    slot.local.clear();
+    return 0;
+}
+
+int hdfs3_fs_add_local_replica(hdfsFS fs, const char *path, int block, int replica, const char *data_path,
+                               const char *meta_path) {
+    PARAMETER_ASSERT(fs && path && std::strlen(path) > 0, -1, EINVAL);
+    PARAMETER_ASSERT(data_path && std::strlen(data_path) > 0 && meta_path && std::strlen(meta_path) > 0, -1, EINVAL);
+    std::lock_guard<std::mutex> lk(fs->mu);
+    auto it = fs->files.find(path);
+    PARAMETER_ASSERT(it != fs->files.end() && it->second.located, -1, ENOENT);
+    FileEntry &e = it->second;
+    const auto &lbs = e.located_blocks.blocks;
+    PARAMETER_ASSERT(block >= 0 && size_t(block) < lbs.size() && replica >= 0 &&
+                         replica < lbs[size_t(block)].n_replicas,
+                     -1, EINVAL);
+    for (const LocalFiles &l : e.local) PARAMETER_ASSERT(l.block != block || l.replica != replica, -1, EINVAL);
+    e.local.push_back(LocalFiles{block, replica, data_path, meta_path});
+    return 0;
+}
+
+int hdfs3_fs_set_local_read(hdfsFS fs, int on, const hdfs3_local_opts *lopts) {
+    PARAMETER_ASSERT(fs, -1, EINVAL);
+    PARAMETER_ASSERT(!lopts || (!(lopts->flags & ~HDFS3_LOCAL_CRC32_AS_ZLIB) && lopts->buffer_size <= (1 << 30)), -1,
+                     EINVAL);
+    std::lock_guard<std::mutex> lk(fs->mu);
+    fs->local_read = on != 0;
+    fs->lopts = lopts ? *lopts : hdfs3_local_opts{0, 1, 0, 0, 0};
     return 0;
 }
 
@@ -342,6 +379,12 @@ hdfsFile hdfsOpenFile(hdfsFS fs, const char *path, int flags, int bufferSize, sh
                                   fs->client_name.c_str(), &fs->ropts, &file->in);
             if (rc == 0 && fs->readahead_blocks > 0)
                 rc = hdfs3_input_set_readahead(file->in, fs->readahead_blocks, fs->readahead_bytes);
+            if (rc == 0 && fs->local_read && !e.local.empty()) {
+                std::vector<hdfs3_local_replica> lr;
+                for (const LocalFiles &l : e.local)
+                    lr.push_back(hdfs3_local_replica{l.block, l.replica, l.data.c_str(), l.meta.c_str()});
+                rc = hdfs3_input_set_local_replicas(file->in, lr.data(), int(lr.size()), &fs->lopts);
+            }
             if (rc < 0 && file->in) {
                 hdfs3_input_close(file->in);
                 file->in = nullptr;
@@ -381,6 +424,7 @@ void complete_written_file(hdfsFS fs, hdfsFile file) {
     FileEntry &slot = fs->files[file->path];
     slot.located_blocks.assign(all.data(), int(all.size()));
     slot.located = true;
+    slot.local.clear();  // the entry was replaced: its replicas are the pipeline's nodes now
     if (file->block_size_known) slot.block_size = file->block_size;  // what FileStatus reports from now on
 }
 }  // namespace

@@ -8,6 +8,15 @@
 // max_bytes of the block, so their receiver threads read and verify ahead while block i is
 // consumed. When the cursor reaches block i+1 its reader simply becomes the current one:
 // read(), failover and EIO behave exactly as for a reader opened on demand.
+//
+// Short-circuit replicas (hdfs3_input_set_local_replicas; setupBlockReader's LocalBlockReader branch,
+// :392-416): when the chosen node has a registered, still-valid local replica the block is read through
+// hdfs3_local_reader instead. A local reader that cannot be opened or fails while reading invalidates
+// that replica for the stream's life (info->setValid(false), :410-413) and the SAME node is read through
+// the remote reader from the cursor on; the node is not failed (temporaryDisableLocalRead, :690-706).
+// Stricter than the reference in one place: a forward seek skips through the local reader by reading and
+// discarding, so the buffers skipped over are verified (LocalBlockReader::skip, :233-280, does not verify
+// them); a bad one abandons the local replica at the seek's target.
 #include <algorithm>
 #include <cerrno>
 #include <cstdlib>
@@ -21,6 +30,7 @@
 #include "block_reader.h"
 #include "hdfs3_client.h"
 #include "hdfs3_crc.h"
+#include "local_reader.h"
 
 using namespace hdfs3crc;
 
@@ -50,6 +60,37 @@ struct Ahead {
     Node node;
 };
 
+// a short-circuit replica the caller registered (what ReadShortCircuitInfoBuilder::fetchOrCreate returns)
+struct LocalReplica {
+    int block, replica;
+    std::string data, meta;
+    bool valid = true;  // ReadShortCircuitInfo::isValid: cleared when a local reader on it failed
+};
+
+// The stream's reader on one block: a remote block reader or a local one, never both.
+struct Reader {
+    hdfs3_block_reader *remote = nullptr;
+    hdfs3_local_reader *local = nullptr;
+    int block = -1, replica = -1;  // local: the table entry it was opened on
+
+    explicit operator bool() const { return remote || local; }
+    // into host memory, or (dev) into device memory
+    int32_t read(uint8_t *buf, int32_t size, bool dev) const {
+        if (local) return dev ? hdfs3_local_reader_read_dev(local, buf, size) : hdfs3_local_reader_read(local, buf, size);
+        return dev ? hdfs3_block_reader_read_dev(remote, buf, size) : hdfs3_block_reader_read(remote, buf, size);
+    }
+    int64_t available() const {
+        return local ? hdfs3_local_reader_available(local) : remote ? hdfs3_block_reader_available(remote) : 0;
+    }
+    // the failure is this host's GPU or memory, not the replica's
+    bool host_fault() const { return local ? local_reader_host_fault(local) : block_reader_local_fault(remote); }
+    void close() {
+        if (remote) hdfs3_block_reader_close(remote);
+        if (local) hdfs3_local_reader_close(local);
+        *this = Reader();
+    }
+};
+
 // hdfs.h convention: errno + -1; the message goes where hdfs3_crc_last_error reads it
 int posix_fail(int err, const std::string &msg) {
     fail(-err, "%s", msg.c_str());
@@ -68,10 +109,13 @@ struct hdfs3_input_stream {
     int64_t cursor = 0;
     int64_t end_of_cur_block = 0;
     int cur = -1;
-    hdfs3_block_reader *reader = nullptr;
+    Reader reader;
     Node cur_node;
     std::vector<Node> failed;  // failedNodes
     uint64_t failovers = 0, opened = 0;
+    std::vector<LocalReplica> local;  // hdfs3_input_set_local_replicas
+    hdfs3_local_opts local_opts{0, 1, 0, 0, 0};  // buffer_size, window_buffers, flags; 0: the reader's defaults
+    uint64_t local_opened = 0, local_fallbacks = 0, local_bytes = 0;
     std::string last_error;
     int ahead_blocks = 0;           // hdfs3_input_set_readahead
     int64_t ahead_bytes = 0;
@@ -87,10 +131,23 @@ struct hdfs3_input_stream {
     }
 
     void drop_reader() {
-        if (reader) hdfs3_block_reader_close(reader);
-        reader = nullptr;
+        reader.close();
         if (reader_ctx) ctx_release(reader_ctx);  // after the reader: its arenas go back into it
         reader_ctx = nullptr;
+    }
+
+    // the registered local replica of block i's replica k while it is still valid
+    LocalReplica *local_replica(int i, int k) {
+        for (LocalReplica &l : local)
+            if (l.block == i && l.replica == k) return l.valid ? &l : nullptr;
+        return nullptr;
+    }
+
+    // a local reader could not be opened or failed while reading: the replica is not tried again by this
+    // stream, and its node is read remotely (the table may have been replaced since the reader opened)
+    void abandon_local(int i, int k) {
+        if (LocalReplica *l = local_replica(i, k)) l->valid = false;
+        ++local_fallbacks;
     }
 
     static void close_ahead(Ahead &a) {
@@ -116,7 +173,7 @@ struct hdfs3_input_stream {
     void schedule_ahead(int i) {
         for (auto it = ahead.begin(); it != ahead.end(); ++it) {
             if (it->block != i) continue;
-            reader = it->reader;
+            reader.remote = it->reader;
             reader_ctx = it->ctx;
             cur_node = it->node;
             ahead.erase(it);
@@ -130,6 +187,9 @@ struct hdfs3_input_stream {
             if (at != ahead.end() && at->block == j) continue;
             const Block &b = blocks[size_t(j)];
             if (b.length <= 0 || b.replicas.empty()) continue;
+            // a block that will be read from a local replica is not fetched over the socket as well: the
+            // local reader's own loader thread reads its windows ahead
+            if (local_replica(j, 0)) continue;
             const int64_t want = std::min<int64_t>(b.length, ahead_bytes > 0 ? ahead_bytes : b.length);
             // the stream's rings (ahead_blocks of them plus the current reader's) fit the pool's pinned
             // cap, so the pool can keep them for the stream's next blocks and the next stream: with
@@ -174,9 +234,9 @@ struct hdfs3_input_stream {
     }
 
     // setupBlockReader (:364-450) for [start, start+len) of block b; -errno
-    int setup(const Block &b, int64_t start, int64_t len, hdfs3_block_reader **out, Node *node,
-              uint8_t *dest = nullptr) {
+    int setup(const Block &b, int64_t start, int64_t len, Reader *out, Node *node, uint8_t *dest = nullptr) {
         std::string why;
+        const int bi = int(&b - blocks.data());
         for (;;) {
             const Node *n = best_node(b);
             if (!n) {
@@ -184,10 +244,36 @@ struct hdfs3_input_stream {
                              std::to_string(b.id.block_id) + (why.empty() ? "" : " (last: " + why + ")");
                 return -EIO;
             }
+            const int k = int(n - b.replicas.data());
+            if (const LocalReplica *l = local_replica(bi, k)) {
+                hdfs3_local_opts lo = local_opts;
+                lo.device = opts.device;
+                lo.verify = opts.verify;
+                LocalOpenExtra extra;
+                extra.range_end = start + len;
+                extra.replica = true;
+                const int rc = open_local_reader(l->data.c_str(), l->meta.c_str(), b.length, start, &lo, &extra, &out->local);
+                if (rc == 0) {
+                    out->block = bi;
+                    out->replica = k;
+                    *node = *n;
+                    ++local_opened;
+                    return 0;
+                }
+                // this host's GPU or memory: neither the replica's fault nor the node's
+                if (extra.host_fault || rc == -ENOMEM || rc == -ENODEV || rc == -ENOTSUP) {
+                    last_error = hdfs3_crc_last_error();
+                    return rc;
+                }
+                // the same node again, through the remote reader; it does not go on the failed list
+                why = hdfs3_crc_last_error();
+                abandon_local(bi, k);
+                continue;
+            }
             hdfs3_block_id id = b.id;
             id.pool_id = b.pool.c_str();
             const int rc = open_block_reader(n->host.c_str(), n->port, &id, start, len, client_name.c_str(), &opts,
-                                             ctx, out, 0, dest);
+                                             ctx, &out->remote, 0, dest);
             if (rc == 0) {
                 *node = *n;
                 ++opened;
@@ -212,12 +298,7 @@ struct hdfs3_input_stream {
         else if (!ahead.empty()) drop_ahead(i);
     }
 
-    // the block reader's read into host memory, or (dev) into device memory
-    static int32_t reader_read(hdfs3_block_reader *r, uint8_t *buf, int32_t size, bool dev) {
-        return dev ? hdfs3_block_reader_read_dev(r, buf, size) : hdfs3_block_reader_read(r, buf, size);
-    }
-
-    // readOneBlock (:616-712); dev: buf is device memory (hdfs3_block_reader_read_dev)
+    // readOneBlock (:616-712); dev: buf is device memory (the readers' read_dev)
     int32_t read_one_block(uint8_t *buf, int32_t size, bool dev) {
         const Block &b = blocks[cur];
         for (;;) {
@@ -226,9 +307,10 @@ struct hdfs3_input_stream {
                 if (int rc = setup(b, off, b.length - off, &reader, &cur_node)) return rc;
             }
             const int32_t todo = int32_t(std::min<int64_t>(size, end_of_cur_block - cursor));
-            const int32_t n = reader_read(reader, buf, todo, dev);
+            const int32_t n = reader.read(buf, todo, dev);
             if (n > 0) {
                 cursor += n;
+                if (reader.local) local_bytes += uint64_t(n);
                 return n;
             }
             // a destination that is not this device's memory is the caller's mistake, not the replica's
@@ -241,7 +323,7 @@ struct hdfs3_input_stream {
             // reader does not need: that block is read again on demand from the cursor on the
             // stream's ctx, and only a fault there is reported (same bytes and errors as with
             // read-ahead off)
-            if (block_reader_local_fault(reader)) {
+            if (reader.host_fault()) {
                 last_error = hdfs3_crc_last_error();
                 const bool prefetched = reader_ctx != nullptr;
                 drop_reader();
@@ -250,6 +332,13 @@ struct hdfs3_input_stream {
                     continue;
                 }
                 return n < 0 ? n : -EIO;
+            }
+            // a local reader's ChecksumException or file error (:690-706): what it returned before stays
+            // delivered; the same node is read remotely from the cursor on, and is not failed
+            if (reader.local) {
+                abandon_local(reader.block, reader.replica);
+                drop_reader();
+                continue;
             }
             // ChecksumException or I/O failure: this replica is bad, try another (:682-708)
             ++failovers;
@@ -276,7 +365,7 @@ struct hdfs3_input_stream {
         saved.swap(failed);
         int rc = 0;
         for (;;) {
-            hdfs3_block_reader *r = nullptr;
+            Reader r;
             Node node;
             // the range's one destination goes to the reader, which copies each packet there while it is hot
             // (round 6; 8 concurrent preads: client CPU per GiB 1.28-1.41x -> 0.98-1.16x the reference
@@ -288,18 +377,27 @@ struct hdfs3_input_stream {
             int64_t got = 0;
             int32_t n = 0;
             while (got < len) {
-                n = reader_read(r, out + got, int32_t(std::min<int64_t>(len - got, 1 << 30)), dev);
+                n = r.read(out + got, int32_t(std::min<int64_t>(len - got, 1 << 30)), dev);
                 if (n <= 0) break;
                 got += n;
             }
-            const bool local = block_reader_local_fault(r);
+            const bool local = r.host_fault();
             if (local) last_error = hdfs3_crc_last_error();
-            hdfs3_block_reader_close(r);
-            if (got == len) break;
+            const bool short_circuit = r.local != nullptr;
+            const int lb = r.block, lk = r.replica;
+            r.close();
+            if (got == len) {
+                if (short_circuit) local_bytes += uint64_t(len);
+                break;
+            }
             if (local || (dev && n == -EINVAL)) {  // this host's GPU or the caller's pointer, not the replica: no failover
                 if (!local) last_error = hdfs3_crc_last_error();
                 rc = n < 0 ? n : -EIO;
                 break;
+            }
+            if (short_circuit) {  // the range again from its first byte, from the same node's remote reader
+                abandon_local(lb, lk);
+                continue;
             }
             ++failovers;
             failed.push_back(node);
@@ -331,7 +429,7 @@ struct hdfs3_input_stream {
             uint8_t scratch[16384];
             bool ok = true;
             while (cursor < pos) {
-                const int32_t n = hdfs3_block_reader_read(reader, scratch, int32_t(std::min<int64_t>(sizeof(scratch), pos - cursor)));
+                const int32_t n = reader.read(scratch, int32_t(std::min<int64_t>(sizeof(scratch), pos - cursor)), false);
                 if (n <= 0) {
                     ok = false;
                     break;
@@ -339,6 +437,9 @@ struct hdfs3_input_stream {
                 cursor += n;
             }
             if (ok) return 0;
+            // a local reader met a bad buffer (or a file error) on the way: the replica is abandoned, and the
+            // read at the target opens the same node's remote reader
+            if (reader.local && !reader.host_fault()) abandon_local(reader.block, reader.replica);
         }
         drop_reader();
         end_of_cur_block = 0;
@@ -442,7 +543,7 @@ int64_t hdfs3_input_tell(hdfs3_input_stream *s) {
 
 int hdfs3_input_available(hdfs3_input_stream *s) {
     if (!s) return posix_fail(EINVAL, "hdfsAvailable: invalid argument");
-    const int64_t a = s->reader ? hdfs3_block_reader_available(s->reader) : 0;
+    const int64_t a = s->reader.available();
     return int(std::min<int64_t>(a, 0x7FFFFFFF));
 }
 
@@ -452,6 +553,42 @@ int hdfs3_input_stats(hdfs3_input_stream *s, uint64_t *failovers, uint64_t *read
     if (!s) return fail(-EINVAL, "null stream");
     if (failovers) *failovers = s->failovers;
     if (readers_opened) *readers_opened = s->opened;
+    return 0;
+}
+
+int hdfs3_input_set_local_replicas(hdfs3_input_stream *s, const hdfs3_local_replica *local, int n,
+                                   const hdfs3_local_opts *lopts) {
+    if (!s || n < 0 || (n && !local)) return fail(-EINVAL, "invalid argument");
+    if (int rc = local_opts_check(lopts)) return rc;
+    std::vector<LocalReplica> table;
+    for (int i = 0; i < n; ++i) {
+        const hdfs3_local_replica &l = local[i];
+        if (l.block < 0 || l.block >= int(s->blocks.size()) || l.replica < 0 ||
+            l.replica >= int(s->blocks[size_t(l.block)].replicas.size()))
+            return fail(-EINVAL, "local replica %d names block %d replica %d, which the stream does not have", i, l.block,
+                        l.replica);
+        if (!l.data_path || !l.meta_path) return fail(-EINVAL, "local replica %d has no data or meta path", i);
+        for (const LocalReplica &t : table)
+            if (t.block == l.block && t.replica == l.replica)
+                return fail(-EINVAL, "block %d replica %d is named twice", l.block, l.replica);
+        table.push_back(LocalReplica{l.block, l.replica, l.data_path, l.meta_path});
+    }
+    s->local.swap(table);
+    s->local_opts = hdfs3_local_opts{0, 1, 0, 0, 0};
+    if (lopts) {
+        s->local_opts.buffer_size = lopts->buffer_size;
+        s->local_opts.window_buffers = lopts->window_buffers;
+        s->local_opts.flags = lopts->flags;
+    }
+    return 0;
+}
+
+int hdfs3_input_local_stats(hdfs3_input_stream *s, uint64_t *local_readers_opened, uint64_t *local_fallbacks,
+                            uint64_t *local_bytes) {
+    if (!s) return fail(-EINVAL, "null stream");
+    if (local_readers_opened) *local_readers_opened = s->local_opened;
+    if (local_fallbacks) *local_fallbacks = s->local_fallbacks;
+    if (local_bytes) *local_bytes = s->local_bytes;
     return 0;
 }
 

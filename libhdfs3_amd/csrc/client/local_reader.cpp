@@ -50,6 +50,8 @@
 #include "../numa.h"
 #include "hdfs3_client.h"
 #include "hdfs3_crc.h"
+#include "local_range.h"
+#include "local_reader.h"
 #include "wire.h"
 
 using namespace hdfs3crc;
@@ -256,6 +258,9 @@ struct hdfs3_local_reader {
     std::thread loader;
     int error = 0;
     std::string error_msg;
+    // the failure is the replica's (its files or their contents); every other failure is this host's
+    // (local_reader_host_fault). Set by the loader before it publishes load_error, by the caller otherwise.
+    std::atomic<bool> replica_fault{false};
     std::atomic<uint64_t> batches{0};
     // mapped mode
     uint8_t *map = nullptr;
@@ -337,6 +342,7 @@ struct hdfs3_local_reader {
         if (w.src == w.a.h) {
             if (int rc = CopyPool::get().pread(data_fd, w.a.h, w.len, start)) {
                 load_msg = "LocalBlockReader: failed to read the block file";
+                replica_fault = true;
                 return rc;
             }
         }
@@ -349,6 +355,7 @@ struct hdfs3_local_reader {
         const uint64_t chunks = (uint64_t(w.len) + chunk_size - 1) / chunk_size;
         if (int rc = pread_fully(meta_fd, w.a.h + cap_data, 4 * chunks, kMetaHeader + 4 * int64_t(chunk0))) {
             load_msg = "LocalBlockReader: failed to read the meta file";
+            replica_fault = true;
             return rc;
         }
         HIP_OK(hipMemcpyAsync(w.a.d, h2d_src, w.len, hipMemcpyHostToDevice, ctx->stream));
@@ -456,6 +463,7 @@ struct hdfs3_local_reader {
                 cursor = begin + n;
             }
             if (w.bad_chunk >= 0 && cursor >= end) {
+                replica_fault = true;
                 sticky(-EIO, "ChecksumException: LocalBlockReader checksum not match for block (chunk " +
                                  std::to_string(w.bad_chunk) + ")");
                 return total ? total : error;
@@ -693,6 +701,7 @@ struct hdfs3_local_reader {
             give_slot_back(w, s);
         }
         if (bad_chunk >= 0 && cursor >= end) {
+            replica_fault = true;
             sticky(-EIO, "ChecksumException: LocalBlockReader checksum not match for block (chunk " +
                              std::to_string(bad_chunk) + ")");
             return total ? total : error;
@@ -745,11 +754,20 @@ struct hdfs3_local_reader {
     }
 };
 
-extern "C" {
+namespace hdfs3crc {
 
-int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_t num_bytes, int64_t offset,
-                            const hdfs3_local_opts *opts, hdfs3_local_reader **out) {
+bool local_reader_host_fault(const hdfs3_local_reader *r) { return r && r->error && !r->replica_fault.load(); }
+
+int local_opts_check(const hdfs3_local_opts *opts) {
+    if (opts && (opts->flags & ~HDFS3_LOCAL_CRC32_AS_ZLIB)) return fail(-EINVAL, "unknown local reader flags");
+    if (opts && opts->buffer_size > kMaxBuffer) return fail(-EINVAL, "LocalBlockReader: local buffer above 1 GiB");
+    return 0;
+}
+
+int open_local_reader(const char *data_path, const char *meta_path, int64_t num_bytes, int64_t offset,
+                      const hdfs3_local_opts *opts, LocalOpenExtra *extra, hdfs3_local_reader **out) {
     if (!out || !data_path || !meta_path || offset < 0) return fail(-EINVAL, "invalid argument");
+    const bool replica = extra && extra->replica;
     *out = nullptr;
     hdfs3_local_reader *r = new (std::nothrow) hdfs3_local_reader();
     if (!r) return fail(-ENOMEM, "reader allocation");
@@ -769,8 +787,10 @@ int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_
     struct stat st;
     if (fstat(r->data_fd, &st) != 0) return bail(fail(-errno, "fstat failed"));
     r->length = num_bytes > 0 ? num_bytes : int64_t(st.st_size);
-    if (num_bytes > int64_t(st.st_size)) return bail(fail(-EIO, "block file shorter than the block length"));
+    const bool short_file = r->length > int64_t(st.st_size);
+    if (short_file && !replica) return bail(fail(-EIO, "block file shorter than the block length"));
     if (offset > r->length) return bail(fail(-EINVAL, "offset beyond the block"));
+    if (short_file && offset > int64_t(st.st_size)) return bail(fail(-EIO, "LocalBlockReader: offset beyond the block file"));
     if (int rc = r->open_meta(opts ? opts->verify != 0 : true)) return bail(rc);
     if (r->verify) {  // chunk-rounded local buffer (:112-116); reads start on a chunk (skip, :232-263)
         const int64_t rounded = (int64_t(r->buffer_size) + r->chunk_size - 1) / r->chunk_size * r->chunk_size;
@@ -784,6 +804,8 @@ int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_
         r->first = offset;
     }
     r->cursor = offset;
+    // a range read ends with the buffer that holds the range's last byte: from here on that is the block's end
+    if (extra) r->length = local_read_limit(r->first, extra->range_end, r->buffer_size, r->length);
     // whole buffers per window, at least one (the buffer itself is at most 1 GiB)
     r->window = uint32_t(std::max<int64_t>(1, std::min<int64_t>(wbuf, kMaxBuffer / r->buffer_size)) * r->buffer_size);
     // mapped mode: verification off always (copies straight from the page cache); verified
@@ -791,7 +813,8 @@ int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_
     // and the window size page multiples), so windows register disjoint page ranges
     const char *mm = getenv("HDFS3_LOCAL_MMAP");
     r->map_verified = mm && mm[0] == '1' && r->verify && r->first % kPage == 0 && r->window % kPage == 0;
-    if (r->length > 0 && !(mm && mm[0] == '0') && (!r->verify || r->map_verified)) {
+    // (a block file shorter than the block is never mapped: the pages past its end would fault, the pread fails)
+    if (r->length > 0 && !short_file && !(mm && mm[0] == '0') && (!r->verify || r->map_verified)) {
         r->map_len = size_t((r->length + kPage - 1) / kPage * kPage);
         void *m = mmap(nullptr, r->map_len, PROT_READ, MAP_SHARED, r->data_fd, 0);
         if (m != MAP_FAILED) {
@@ -803,6 +826,8 @@ int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_
     }
     r->cap_data = (size_t(r->window) + 255) & ~size_t(255);
     const size_t crc_bytes = r->verify ? 4 * ((size_t(r->window) + r->chunk_size - 1) / r->chunk_size) : 0;
+    // the files are in order: whatever fails from here on is this host's
+    if (extra) extra->host_fault = true;
     // the windows live on `device`, whatever the calling thread's current device is
     DeviceGuard guard(device);
     LocalResources pooled;
@@ -853,8 +878,18 @@ int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_
     } else {
         r->load_done = true;
     }
+    if (extra) extra->host_fault = false;
     *out = r;
     return 0;
+}
+
+}  // namespace hdfs3crc
+
+extern "C" {
+
+int hdfs3_local_reader_open(const char *data_path, const char *meta_path, int64_t num_bytes, int64_t offset,
+                            const hdfs3_local_opts *opts, hdfs3_local_reader **out) {
+    return open_local_reader(data_path, meta_path, num_bytes, offset, opts, nullptr, out);
 }
 
 int32_t hdfs3_local_reader_read(hdfs3_local_reader *r, void *buf, int32_t len) {

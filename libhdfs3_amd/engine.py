@@ -12,6 +12,7 @@ Every call runs on the GPU; there is no host fallback.
 from __future__ import annotations
 
 import ctypes
+import os
 from ctypes import byref, c_int, c_int64, c_void_p
 
 import numpy as np
@@ -612,6 +613,28 @@ class InputStream:
         check("hdfs3_input_readahead_stats", self._lib.hdfs3_input_readahead_stats(self.s, byref(a), byref(lf)))
         return {"failovers": f.value, "readers_opened": o.value, "prefetch_readers_opened": a.value,
                 "prefetch_local_faults": lf.value}
+
+    def set_local_replicas(self, replicas, *, buffer_size: int = 0, window_buffers: int = 0, flags: int = 0) -> None:
+        """hdfs3_input_set_local_replicas: `replicas` = [(block, replica, data_path, meta_path), ...] names
+        the replicas that are on this machine (an empty list clears the table); blocks whose chosen node has
+        one are read through the short-circuit reader, falling back to the same datanode when it fails.
+        buffer_size / window_buffers 0 = the local reader's defaults."""
+        arr = (_native.LocalReplica * max(1, len(replicas)))()
+        for i, (block, replica, data, meta) in enumerate(replicas):
+            arr[i] = _native.LocalReplica(block, replica, None if data is None else os.fsencode(data),
+                                          None if meta is None else os.fsencode(meta))
+        opts = _native.LocalOpts(0, 1, buffer_size, window_buffers, flags)
+        check("hdfs3_input_set_local_replicas",
+              self._lib.hdfs3_input_set_local_replicas(self.s, arr, len(replicas), byref(opts)), self._lib)
+
+    def local_stats(self):
+        """hdfs3_input_local_stats: local readers opened, local replicas abandoned for the same node's
+        remote reader, bytes handed out from local readers."""
+        from ctypes import c_uint64
+        o, f, b = c_uint64(), c_uint64(), c_uint64()
+        check("hdfs3_input_local_stats", self._lib.hdfs3_input_local_stats(self.s, byref(o), byref(f), byref(b)),
+              self._lib)
+        return {"local_readers_opened": o.value, "local_fallbacks": f.value, "local_bytes": b.value}
 
     def set_readahead(self, blocks: int, max_bytes_per_block: int = 0) -> None:
         """hdfs3_input_set_readahead: blocks i+1 .. i+blocks read by background threads while

@@ -1,0 +1,32 @@
+"""CPU: where the loader of a short-circuit range read stops (csrc/client/local_range.h: the end of the
+buffer_size buffer, counted from the chunk-aligned first byte read, that holds the range's last byte, clipped to
+the block) under AddressSanitizer and UndefinedBehaviorSanitizer, driven by tests/native/local_range_check.cpp,
+a program of its own that includes that header alone."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+from util import REPO
+
+CSRC = os.path.join(REPO, "libhdfs3_amd", "csrc")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_local_range_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "local_range_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", CSRC, os.path.join(REPO, "tests", "native", "local_range_check.cpp"), "-o", str(exe)]
+    subprocess.run(cmd, check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
+               UBSAN_OPTIONS="halt_on_error=1")
+    out = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    assert "local range ok" in out.stdout
+
+
+def test_local_range_header_needs_no_gpu_runtime():
+    with open(os.path.join(CSRC, "client", "local_range.h")) as f:
+        includes = [ln.split()[1] for ln in f if ln.startswith("#include")]
+    assert includes and not [i for i in includes if "hip" in i.lower()], includes
