@@ -16,6 +16,12 @@
 // buffer in a guarded delivery (crc32c_gather.hip) that reads the window's result word on the
 // device, so the caller enqueues it without waiting for the verify (see read_dev_verified).
 //
+// Geometry. Every size and offset here comes from local_layout.h (host arithmetic, checked on the CPU by
+// tests/test_local_layout.py): the buffer, the first byte, the windows, their chunks and .meta words, where a
+// corrupt block's good bytes end (good_end) and the span of a window a read takes. This file holds the files,
+// the mapping, the pool and the threads. The three reads (read, read_dev_plain, read_dev_verified) take their
+// next window through next_ready() and end through finish().
+//
 // Staging. Verification on: a window is pread into its pinned arena by the loader and the
 // helper threads together (a single pread thread was the single-stream limit), DMA'd, and
 // copied out. Verification off: the block file is mmap'd (MappedFileWrapper, MappedFileWrapper.cpp:
@@ -50,7 +56,7 @@
 #include "../numa.h"
 #include "hdfs3_client.h"
 #include "hdfs3_crc.h"
-#include "local_range.h"
+#include "local_layout.h"
 #include "local_reader.h"
 #include "wire.h"
 
@@ -58,11 +64,7 @@ using namespace hdfs3crc;
 
 namespace {
 
-constexpr int kMetaHeader = 7;             // HEADER_SIZE: version 2 + type 1 + bpc 4
 constexpr int kSlots = 3;
-constexpr int32_t kDefaultBuffer = 1 << 20;  // input.localread.default.buffersize
-constexpr int kDefaultWindowBuffers = 4;  // 4 MiB windows: first delivery sooner (docs/DESIGN_HISTORY.md §5.1)
-constexpr int32_t kMaxBuffer = 1 << 30;     // largest local buffer / window
 
 // Window events: HDFS3_LOCAL_BLOCKING_SYNC=1 makes the consumer sleep in hipEventSynchronize
 // (hipEventBlockingSync) instead of spinning, leaving the cores to the copies when many readers
@@ -125,10 +127,13 @@ bool take_pooled(int device, size_t cap, LocalResources *out) {
     return false;
 }
 
-void free_resources(LocalResources &r) {
+// Drops an entry's windows and words. Its ctx is released into the ctx pool, or destroyed outright: an entry
+// dropped to keep the pinned cap, or by a trim, must not move the bytes just refused into the other pool.
+void drop_resources(LocalResources &r, bool destroy_ctx) {
     for (PacketArena &a : r.a) a.release();
     r.dev.release();
-    ctx_release(r.ctx);
+    if (destroy_ctx) hdfs3_crc_ctx_destroy(r.ctx);
+    else ctx_release(r.ctx);
     r.ctx = nullptr;
 }
 
@@ -145,15 +150,6 @@ LocalPoolStats entry_bytes(const LocalResources &r) {
     if (r.dev.h_gate) st.pinned += sizeof(unsigned long long);
     st.entries = 1;
     return st;
-}
-
-// a pooled entry dropped to keep the cap: destroyed outright, as local_pool_trim does. Releasing its
-// ctx into the ctx pool would only move the bytes the cap just refused into the other pool.
-void destroy_resources(LocalResources &r) {
-    for (PacketArena &a : r.a) a.release();
-    r.dev.release();
-    hdfs3_crc_ctx_destroy(r.ctx);
-    r.ctx = nullptr;
 }
 
 // Pooled unless that would take the retained pinned bytes of both pools past the cap
@@ -181,10 +177,10 @@ void give_back(LocalResources r) {
             }
         }
     }
-    for (LocalResources &e : evict) destroy_resources(e);
+    for (LocalResources &e : evict) drop_resources(e, /*destroy_ctx=*/true);
     // not admitted: the windows go, and the ctx takes its own admission into the ctx pool
     // (ctx_release takes pool_admission_mu itself, so this runs after the scope above)
-    if (!keep) free_resources(r);
+    if (!keep) drop_resources(r, /*destroy_ctx=*/false);
 }
 
 // Copies out of a verified window (one thread ~11 GiB/s) and the window preads (one thread
@@ -193,8 +189,7 @@ void give_back(LocalResources r) {
 
 struct Window {
     PacketArena a;            // h/d: [data (cap_data)][crc words]
-    int64_t start = 0;        // block offset of the window's first byte (chunk aligned)
-    uint32_t len = 0;         // data bytes
+    LocalWindow g;            // its bytes of the block, its chunks and their .meta words
     int64_t bad_chunk = -1;   // first mismatching chunk (block-relative), after wait
     bool verified = false;
     const uint8_t *src = nullptr;  // where read() copies from: a.h, or the mapping
@@ -225,11 +220,7 @@ int local_pool_trim() {
         idle.swap(g_pool);
     }
     // destroyed outright, not released: a trim leaves no context behind in either pool
-    for (LocalResources &e : idle) {
-        for (PacketArena &a : e.a) a.release();
-        e.dev.release();
-        hdfs3_crc_ctx_destroy(e.ctx);
-    }
+    for (LocalResources &e : idle) drop_resources(e, /*destroy_ctx=*/true);
     return int(idle.size());
 }
 }  // namespace hdfs3crc
@@ -241,11 +232,7 @@ struct hdfs3_local_reader {
     int checksum_type = 2;
     uint32_t flags = 0;                      // hdfs3_local_opts.flags
     uint32_t chunk_size = 0;
-    int32_t buffer_size = kDefaultBuffer;    // localBufferSize (chunk-rounded when verifying)
-    uint32_t window = 0;                     // bytes per GPU window (multiple of buffer_size)
-    size_t cap_data = 0;
-    int64_t length = 0;                      // block length
-    int64_t first = 0;                       // first byte the loader reads (chunk aligned)
+    LocalLayout lay;                         // buffer, first byte, end, windows (local_layout.h)
     int64_t cursor = 0;                      // next byte handed to the caller
 
     std::mutex mu;
@@ -281,7 +268,7 @@ struct hdfs3_local_reader {
 
     // LocalBlockReader ctor (:46-130): meta header, engine selection, buffer size
     int open_meta(bool want_verify) {
-        uint8_t h[kMetaHeader];
+        uint8_t h[kLocalMetaHeader];
         if (int rc = pread_fully(meta_fd, h, sizeof(h), 0)) return sticky(rc, "LocalBlockReader: cannot read the meta header");
         const int version = (h[0] << 8) | h[1];
         if (version != 1)
@@ -318,8 +305,9 @@ struct hdfs3_local_reader {
 
     // ---- loader thread ------------------------------------------------------------------
     int load(Window &w, int64_t start) {
-        w.start = start;
-        w.len = uint32_t(std::min<int64_t>(window, length - start));
+        w.g = lay.window_at(start);
+        const uint32_t len = w.g.len;
+        const size_t cap_data = lay.cap_data;
         w.bad_chunk = -1;
         w.verified = false;
         w.src = w.a.h;
@@ -329,7 +317,7 @@ struct hdfs3_local_reader {
             w.src = map + start;  // no staging at all: read() copies from the page cache
         } else if (map && map_verified && start % kPage == 0) {
             // pin the window's page-cache pages in place; the DMA reads them directly
-            const size_t reg_len = size_t(std::min<int64_t>((start + w.len + kPage - 1) / kPage * kPage,
+            const size_t reg_len = size_t(std::min<int64_t>((start + len + kPage - 1) / kPage * kPage,
                                                             int64_t(map_len)) - start);
             if (hipHostRegister(map + start, reg_len, hipHostRegisterReadOnly) == hipSuccess) {
                 w.reg = map + start;
@@ -340,7 +328,7 @@ struct hdfs3_local_reader {
             }
         }
         if (w.src == w.a.h) {
-            if (int rc = CopyPool::get().pread(data_fd, w.a.h, w.len, start)) {
+            if (int rc = CopyPool::get().pread(data_fd, w.a.h, len, start)) {
                 load_msg = "LocalBlockReader: failed to read the block file";
                 replica_fault = true;
                 return rc;
@@ -351,17 +339,15 @@ struct hdfs3_local_reader {
             w.verified = true;
             return 0;
         }
-        const uint64_t chunk0 = uint64_t(start) / chunk_size;
-        const uint64_t chunks = (uint64_t(w.len) + chunk_size - 1) / chunk_size;
-        if (int rc = pread_fully(meta_fd, w.a.h + cap_data, 4 * chunks, kMetaHeader + 4 * int64_t(chunk0))) {
+        if (int rc = pread_fully(meta_fd, w.a.h + cap_data, w.g.meta_bytes, w.g.meta_off)) {
             load_msg = "LocalBlockReader: failed to read the meta file";
             replica_fault = true;
             return rc;
         }
-        HIP_OK(hipMemcpyAsync(w.a.d, h2d_src, w.len, hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipMemcpyAsync(w.a.d + cap_data, w.a.h + cap_data, 4 * chunks, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpyAsync(w.a.d, h2d_src, len, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpyAsync(w.a.d + cap_data, w.a.h + cap_data, w.g.meta_bytes, hipMemcpyHostToDevice, ctx->stream));
         HIP_OK(hipMemsetAsync(w.a.d_res, 0, sizeof(unsigned long long), ctx->stream));
-        if (int rc = hdfs3_crc32c_verify_dev_async(ctx, w.a.d, w.len, chunk_size, w.a.d + cap_data,
+        if (int rc = hdfs3_crc32c_verify_dev_async(ctx, w.a.d, len, chunk_size, w.a.d + cap_data,
                                                    /*check_short_tail=*/1, reinterpret_cast<uint64_t *>(w.a.d_res))) {
             load_msg = hdfs3_crc_last_error();
             return rc;
@@ -374,8 +360,8 @@ struct hdfs3_local_reader {
     void run_loader() {
         (void)hipSetDevice(ctx->device);
         bind_thread_to_device(ctx->device);  // preads land next to the GPU (numa.h)
-        int64_t next = first;
-        while (next < length) {
+        int64_t next = lay.first;
+        while (next < lay.length) {
             int s;
             {
                 std::unique_lock<std::mutex> lk(mu);
@@ -394,11 +380,11 @@ struct hdfs3_local_reader {
                 } else {
                     ready.push_back(s);
                 }
-                if (rc || next + slot[s].len >= length) load_done = true;
+                if (rc || slot[s].g.end() >= lay.length) load_done = true;
             }
             cv.notify_all();
             if (rc) return;
-            next += slot[s].len;
+            next = slot[s].g.end();
         }
         std::lock_guard<std::mutex> lk(mu);
         load_done = true;
@@ -417,68 +403,86 @@ struct hdfs3_local_reader {
         if (w.verified) return 0;
         HIP_OK(hipEventSynchronize(w.a.done));
         const unsigned long long r = *w.a.h_res;
-        if (r) w.bad_chunk = int64_t(uint64_t(w.start) / chunk_size) + hdfs3_crc_decode_result(r);
+        if (r) w.bad_chunk = int64_t(w.g.chunk0) + hdfs3_crc_decode_result(r);
         w.verified = true;
         return 0;
+    }
+
+    // The loader's failure as a read met it, captured under mu
+    struct LoadError {
+        int code = 0;
+        std::string msg;
+    };
+
+    // The slot `depth` windows into `ready`; at depth 0 waits until there is one or the loader is done. -1 when
+    // there is none: then, at depth 0, *le holds the loader's error, if it had one.
+    int next_ready(size_t depth, LoadError *le) {
+        std::unique_lock<std::mutex> lk(mu);
+        if (depth == 0) cv.wait(lk, [&] { return !ready.empty() || load_done; });
+        if (ready.size() > depth) return ready[depth];
+        if (depth == 0) *le = LoadError{load_error, load_msg};
+        return -1;
+    }
+
+    int front_slot() {  // -1: `ready` is empty
+        std::lock_guard<std::mutex> lk(mu);
+        return ready.empty() ? -1 : ready.front();
+    }
+
+    // The front window was read to its end (its DMA completed: its `done` event has passed)
+    void give_slot_back(Window &w, int s) {
+        release_pages(w);
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            ready.pop_front();
+            free_slots.push_back(s);
+        }
+        cv.notify_all();
+    }
+
+    // How every read ends, `total` bytes delivered and the cursor behind them. A bad chunk whose good bytes
+    // (up to `end`) are all delivered: sticky -EIO, the bytes now and the error next time. Else a loader's error:
+    // now if nothing was delivered, sticky for the next call if something was.
+    int32_t finish(int32_t total, int64_t bad_chunk, int64_t end, const LoadError &le) {
+        if (bad_chunk >= 0 && cursor >= end) {
+            replica_fault = true;
+            sticky(-EIO, "ChecksumException: LocalBlockReader checksum not match for block (chunk " +
+                             std::to_string(bad_chunk) + ")");
+            return total ? total : error;
+        }
+        if (le.code && !total) return sticky(le.code, le.msg);
+        if (le.code) {
+            error = le.code;
+            error_msg = le.msg;
+        }
+        return total;
     }
 
     int32_t read(uint8_t *out, int32_t len) {
         if (error) return fail(error, "%s", error_msg.c_str());
         if (!out || len <= 0) return fail(-EINVAL, "invalid read buffer");
         int32_t total = 0;
-        while (total < len && cursor < length) {
-            int s;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !ready.empty() || load_done; });
-                if (ready.empty()) {
-                    if (load_error) {
-                        const int code = load_error;
-                        const std::string msg = load_msg;
-                        lk.unlock();
-                        if (total) {
-                            error = code;
-                            error_msg = msg;
-                            return total;
-                        }
-                        return sticky(code, msg);
-                    }
-                    break;
-                }
-                s = ready.front();
-            }
+        int64_t bad_chunk = -1, end = INT64_MAX;  // the front window's first bad chunk and its good end, once known
+        LoadError le;
+        while (total < len && cursor < lay.length) {
+            const int s = next_ready(0, &le);
+            if (s < 0) break;
             Window &w = slot[s];
             if (int rc = wait(w)) return total ? total : sticky(rc, hdfs3_crc_last_error());
-            // deliverable end: everything, or up to the local buffer holding the bad chunk
-            int64_t end = w.start + w.len;
             if (w.bad_chunk >= 0) {
-                const int64_t bad_off = w.bad_chunk * int64_t(chunk_size);
-                end = first + (bad_off - first) / buffer_size * int64_t(buffer_size);
+                bad_chunk = w.bad_chunk;
+                end = lay.good_end(bad_chunk);
             }
-            const int64_t begin = std::max<int64_t>(cursor, w.start);
-            if (begin < end) {
-                const int64_t n = std::min<int64_t>(end - begin, len - total);
-                CopyPool::get().copy(out + total, w.src + (begin - w.start), size_t(n));
-                total += int32_t(n);
-                cursor = begin + n;
+            const LocalSpan sp = LocalLayout::span(w.g, cursor, len - total, end);
+            if (sp.n > 0) {
+                CopyPool::get().copy(out + total, w.src + (sp.begin - w.g.start), size_t(sp.n));
+                total += int32_t(sp.n);
+                cursor = sp.begin + sp.n;
             }
-            if (w.bad_chunk >= 0 && cursor >= end) {
-                replica_fault = true;
-                sticky(-EIO, "ChecksumException: LocalBlockReader checksum not match for block (chunk " +
-                                 std::to_string(w.bad_chunk) + ")");
-                return total ? total : error;
-            }
-            if (cursor >= w.start + w.len) {
-                release_pages(w);  // its DMA completed: wait() saw the event
-                {
-                    std::lock_guard<std::mutex> lk(mu);
-                    ready.pop_front();
-                    free_slots.push_back(s);
-                }
-                cv.notify_all();
-            }
+            if (bad_chunk >= 0 && cursor >= end) break;
+            if (cursor >= w.g.end()) give_slot_back(w, s);
         }
-        return total;
+        return finish(total, bad_chunk, end, le);
     }
 
     // ---- read() into device memory ----------------------------------------------------------
@@ -490,21 +494,6 @@ struct hdfs3_local_reader {
     // the upload; the DEVICE copy needs no wait, the next upload into it is behind the delivery in the stream).
     // The deliveries of one call form a chain over the reader's two gate words, so after a bad window nothing
     // more is written, and the last gate word, read back once at the end, tells where the delivered bytes end.
-    int64_t good_end(int64_t bad_chunk) const {  // read()'s rule: up to the local buffer holding the bad chunk
-        const int64_t bad_off = bad_chunk * int64_t(chunk_size);
-        return first + (bad_off - first) / buffer_size * int64_t(buffer_size);
-    }
-
-    void give_slot_back(Window &w, int s) {
-        release_pages(w);  // its DMA completed: the `done` event has passed
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            ready.pop_front();
-            free_slots.push_back(s);
-        }
-        cv.notify_all();
-    }
-
     int ensure_device_words() {
         if (!dev.done) HIP_OK(hipEventCreateWithFlags(&dev.done, window_event_flags()));
         if (!verify) return 0;
@@ -537,7 +526,7 @@ struct hdfs3_local_reader {
             (void)hipGetLastError();  // a host pointer is the caller's mistake, not a fault of the GPU
             return fail(-EINVAL, "read_dev: the buffer is not device memory of device %d", ctx->device);
         }
-        if (cursor >= length) return 0;
+        if (cursor >= lay.length) return 0;
         if (int rc = ensure_device_words()) return sticky(rc, std::string(hdfs3_crc_last_error()));
         return verify ? read_dev_verified(d_out, len) : read_dev_plain(d_out, len);
     }
@@ -546,43 +535,25 @@ struct hdfs3_local_reader {
     // or the mapping) to d_out with a runtime copy, waited for before the slot goes back. No kernel runs.
     int32_t read_dev_plain(uint8_t *d_out, int32_t len) {
         int32_t total = 0;
-        while (total < len && cursor < length) {
-            int s;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return !ready.empty() || load_done; });
-                if (ready.empty()) {
-                    if (load_error) {
-                        const int code = load_error;
-                        const std::string msg = load_msg;
-                        lk.unlock();
-                        if (total) {
-                            error = code;
-                            error_msg = msg;
-                            return total;
-                        }
-                        return sticky(code, msg);
-                    }
-                    break;
-                }
-                s = ready.front();
-            }
+        LoadError le;
+        while (total < len && cursor < lay.length) {
+            const int s = next_ready(0, &le);
+            if (s < 0) break;
             Window &w = slot[s];
-            const int64_t begin = std::max<int64_t>(cursor, w.start), end = w.start + w.len;
-            if (begin < end) {
-                const int64_t n = std::min<int64_t>(end - begin, len - total);
-                const hipError_t e =
-                    hipMemcpyAsync(d_out + total, w.src + (begin - w.start), size_t(n), hipMemcpyHostToDevice, ctx->stream);
+            const LocalSpan sp = LocalLayout::span(w.g, cursor, len - total);
+            if (sp.n > 0) {
+                const hipError_t e = hipMemcpyAsync(d_out + total, w.src + (sp.begin - w.g.start), size_t(sp.n),
+                                                    hipMemcpyHostToDevice, ctx->stream);
                 int rc = e == hipSuccess ? 0 : hip_err(e, "hipMemcpyAsync");
                 if (!rc) rc = wait_enqueued();
                 if (rc) return sticky(rc, std::string(hdfs3_crc_last_error()));  // nothing is known to be in place
-                total += int32_t(n);
-                cursor = begin + n;
-                dev_bytes.fetch_add(uint64_t(n), std::memory_order_relaxed);
+                total += int32_t(sp.n);
+                cursor = sp.begin + sp.n;
+                dev_bytes.fetch_add(uint64_t(sp.n), std::memory_order_relaxed);
             }
-            if (cursor >= end) give_slot_back(w, s);
+            if (cursor >= w.g.end()) give_slot_back(w, s);
         }
-        return total;
+        return finish(total, -1, INT64_MAX, le);
     }
 
     int32_t read_dev_verified(uint8_t *d_out, int32_t len) {
@@ -592,15 +563,10 @@ struct hdfs3_local_reader {
         bool enqueued = false, chained = false, halt = false;
         int64_t bad_chunk = -1;     // the first bad chunk (block-relative), once a bad window is known,
         int64_t end = INT64_MAX;    // and where the deliverable bytes end before it
-        int load_code = 0;
-        std::string load_text;
+        LoadError le;
         // the front window was wholly enqueued: wait for its result; a good one's slot goes back to the loader
         auto settle_front = [&]() -> int {
-            int s;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                s = ready.front();
-            }
+            const int s = front_slot();
             Window &w = slot[s];
             if (int rc = wait(w)) return rc;
             if (w.bad_chunk >= 0) {
@@ -611,18 +577,8 @@ struct hdfs3_local_reader {
             --held;
             return 0;
         };
-        while (!halt && pos - from < len && pos < length) {
-            int s = -1;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                if (held == 0) cv.wait(lk, [&] { return !ready.empty() || load_done; });
-                if (ready.size() > held) {
-                    s = ready[held];
-                } else if (held == 0) {
-                    load_code = load_error;
-                    load_text = load_msg;
-                }
-            }
+        while (!halt && pos - from < len && pos < lay.length) {
+            const int s = next_ready(held, &le);
             if (s < 0) {
                 if (held == 0) break;  // the loader finished, or failed
                 // nothing left to enqueue: only now wait for the oldest window's event, for its slot
@@ -630,29 +586,26 @@ struct hdfs3_local_reader {
                 continue;
             }
             Window &w = slot[s];
-            const int64_t begin = std::max<int64_t>(pos, w.start);
-            int64_t upto = w.start + w.len;
             // a window an earlier call found bad stays at the front for the reader's life: the host knows where
             // its good bytes end, and the delivery needs no gate (the chain's own stays closed)
             const bool known_bad = w.verified && w.bad_chunk >= 0;
             if (known_bad) {
                 bad_chunk = w.bad_chunk;
-                end = good_end(bad_chunk);
-                upto = std::min(upto, end);
+                end = lay.good_end(bad_chunk);
                 halt = true;
             }
-            const int64_t n = std::min<int64_t>(upto - begin, len - (begin - from));
-            if (n > 0) {
-                const CopyRange rg{uint64_t(begin - w.start), uint64_t(begin - from), uint64_t(n)};
+            const LocalSpan sp = LocalLayout::span(w.g, pos, len - (pos - from), end);
+            if (sp.n > 0) {
+                const CopyRange rg{uint64_t(sp.begin - w.g.start), uint64_t(sp.begin - from), uint64_t(sp.n)};
                 const DeliverGuard g{reinterpret_cast<const uint64_t *>(w.a.d_res),
                                      known_bad ? nullptr : dev.d_gate + gate_cur,
                                      known_bad ? nullptr : dev.d_gate + (gate_cur ^ 1),
                                      0,
-                                     uint64_t(w.start) / chunk_size,
-                                     uint64_t(buffer_size),
+                                     w.g.chunk0,
+                                     uint64_t(lay.buffer_size),
                                      chunk_size};
                 unsigned launched = 0;
-                const int rc = deliver_dev(ctx, d_out, size_t(len), w.a.d, w.len, &rg, 1, g, &launched);
+                const int rc = deliver_dev(ctx, d_out, size_t(len), w.a.d, w.g.len, &rg, 1, g, &launched);
                 dev_launches.fetch_add(launched, std::memory_order_relaxed);
                 if (rc) return sticky(rc, std::string(hdfs3_crc_last_error()));  // nothing is known to be in place
                 enqueued = true;
@@ -660,9 +613,9 @@ struct hdfs3_local_reader {
                     gate_cur ^= 1;
                     chained = true;
                 }
-                pos = begin + n;
+                pos = sp.begin + sp.n;
             }
-            if (halt || pos < w.start + w.len) break;  // a window consumed in part stays at the front
+            if (halt || pos < w.g.end()) break;  // a window consumed in part stays at the front
             ++held;
         }
         // the returned bytes are in place when the call returns: the chain's last gate word comes back behind
@@ -678,7 +631,7 @@ struct hdfs3_local_reader {
             if (rc) return sticky(rc, std::string(hdfs3_crc_last_error()));
             if (chained && *dev.h_gate) {
                 bad_chunk = hdfs3_crc_decode_result(*dev.h_gate);
-                end = good_end(bad_chunk);
+                end = lay.good_end(bad_chunk);
             }
         }
         const int64_t reached = std::min(pos, std::max(end, from));
@@ -687,34 +640,14 @@ struct hdfs3_local_reader {
         dev_bytes.fetch_add(uint64_t(total), std::memory_order_relaxed);
         // every window a delivery was enqueued from has passed its event by now: the good ones this call
         // consumed go back, a bad one stays (and everything behind it)
-        for (;;) {
-            int s;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (ready.empty()) break;
-                s = ready.front();
-            }
+        for (int s; (s = front_slot()) >= 0;) {
             Window &w = slot[s];
-            if (w.start >= pos) break;  // not touched
+            if (w.g.start >= pos) break;  // not touched
             if (int rc = wait(w)) return sticky(rc, std::string(hdfs3_crc_last_error()));
-            if (w.bad_chunk >= 0 || cursor < w.start + w.len) break;
+            if (w.bad_chunk >= 0 || cursor < w.g.end()) break;
             give_slot_back(w, s);
         }
-        if (bad_chunk >= 0 && cursor >= end) {
-            replica_fault = true;
-            sticky(-EIO, "ChecksumException: LocalBlockReader checksum not match for block (chunk " +
-                             std::to_string(bad_chunk) + ")");
-            return total ? total : error;
-        }
-        if (load_code) {
-            if (total) {
-                error = load_code;
-                error_msg = load_text;
-                return total;
-            }
-            return sticky(load_code, load_text);
-        }
-        return total;
+        return finish(total, bad_chunk, end, le);
     }
 
     int64_t available() {
@@ -722,7 +655,7 @@ struct hdfs3_local_reader {
         int64_t a = 0;
         for (int s : ready)
             if (slot[s].verified && slot[s].bad_chunk < 0)
-                a += slot[s].start + slot[s].len - std::max<int64_t>(cursor, slot[s].start);
+                a += LocalLayout::available_in(slot[s].g, cursor);
         return a;
     }
 
@@ -746,7 +679,7 @@ struct hdfs3_local_reader {
             if (clean && res.a[kSlots - 1].done)
                 give_back(res);
             else
-                free_resources(res);
+                drop_resources(res, /*destroy_ctx=*/false);
         }
         if (map) munmap(map, map_len);
         if (data_fd >= 0) ::close(data_fd);
@@ -760,8 +693,24 @@ bool local_reader_host_fault(const hdfs3_local_reader *r) { return r && r->error
 
 int local_opts_check(const hdfs3_local_opts *opts) {
     if (opts && (opts->flags & ~HDFS3_LOCAL_CRC32_AS_ZLIB)) return fail(-EINVAL, "unknown local reader flags");
-    if (opts && opts->buffer_size > kMaxBuffer) return fail(-EINVAL, "LocalBlockReader: local buffer above 1 GiB");
+    if (opts && opts->buffer_size > kLocalMaxBuffer) return fail(-EINVAL, "LocalBlockReader: local buffer above 1 GiB");
     return 0;
+}
+
+// kSlots windows of `bytes` each: pinned and device arena, result words, event. false: one allocation failed
+// (the reader's destructor frees what was made).
+static bool alloc_windows(Window (&slot)[kSlots], size_t bytes) {
+    for (Window &w : slot) {
+        PacketArena &a = w.a;
+        if (hipHostMalloc(reinterpret_cast<void **>(&a.h), bytes, pinned_host_flags()) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&a.d), bytes) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void **>(&a.d_res), sizeof(unsigned long long)) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void **>(&a.h_res), sizeof(unsigned long long), pinned_host_flags()) != hipSuccess ||
+            hipEventCreateWithFlags(&a.done, window_event_flags()) != hipSuccess)
+            return false;
+        a.cap = bytes;
+    }
+    return true;
 }
 
 int open_local_reader(const char *data_path, const char *meta_path, int64_t num_bytes, int64_t offset,
@@ -775,47 +724,36 @@ int open_local_reader(const char *data_path, const char *meta_path, int64_t num_
         delete r;
         return rc;
     };
+    std::string why;
+    auto refused = [&](int rc) { return bail(fail(rc, "%s", why.c_str())); };
     const int device = opts ? opts->device : 0;
-    if (opts && opts->buffer_size > 0) r->buffer_size = opts->buffer_size;
     if (opts) r->flags = opts->flags;
     if (opts && (opts->flags & ~HDFS3_LOCAL_CRC32_AS_ZLIB)) return bail(fail(-EINVAL, "unknown local reader flags"));
-    const int wbuf = opts && opts->window_buffers > 0 ? opts->window_buffers : kDefaultWindowBuffers;
     r->data_fd = ::open(data_path, O_RDONLY | O_CLOEXEC);
     if (r->data_fd < 0) return bail(fail(-errno, "LocalBlockReader: cannot open block file %s", data_path));
     r->meta_fd = ::open(meta_path, O_RDONLY | O_CLOEXEC);
     if (r->meta_fd < 0) return bail(fail(-errno, "LocalBlockReader: cannot open meta file %s", meta_path));
     struct stat st;
     if (fstat(r->data_fd, &st) != 0) return bail(fail(-errno, "fstat failed"));
-    r->length = num_bytes > 0 ? num_bytes : int64_t(st.st_size);
-    const bool short_file = r->length > int64_t(st.st_size);
+    const int64_t block_len = num_bytes > 0 ? num_bytes : int64_t(st.st_size);
+    const bool short_file = block_len > int64_t(st.st_size);
     if (short_file && !replica) return bail(fail(-EIO, "block file shorter than the block length"));
-    if (offset > r->length) return bail(fail(-EINVAL, "offset beyond the block"));
+    if (int rc = LocalLayout::check_offset(offset, block_len, &why)) return refused(rc);
     if (short_file && offset > int64_t(st.st_size)) return bail(fail(-EIO, "LocalBlockReader: offset beyond the block file"));
     if (int rc = r->open_meta(opts ? opts->verify != 0 : true)) return bail(rc);
-    if (r->verify) {  // chunk-rounded local buffer (:112-116); reads start on a chunk (skip, :232-263)
-        const int64_t rounded = (int64_t(r->buffer_size) + r->chunk_size - 1) / r->chunk_size * r->chunk_size;
-        if (rounded > kMaxBuffer)
-            return bail(fail(-EINVAL, "LocalBlockReader: local buffer of %lld bytes (chunk-rounded) exceeds %d",
-                             (long long)rounded, kMaxBuffer));
-        r->buffer_size = int32_t(rounded);
-        r->first = offset / r->chunk_size * r->chunk_size;
-    } else {
-        if (r->buffer_size > kMaxBuffer) return bail(fail(-EINVAL, "LocalBlockReader: local buffer above 1 GiB"));
-        r->first = offset;
-    }
+    if (int rc = LocalLayout::make(offset, block_len, r->chunk_size, opts ? opts->buffer_size : 0,
+                                   opts ? opts->window_buffers : 0, r->verify, extra ? extra->range_end : 0, &r->lay, &why))
+        return refused(rc);
+    const LocalLayout &lay = r->lay;
     r->cursor = offset;
-    // a range read ends with the buffer that holds the range's last byte: from here on that is the block's end
-    if (extra) r->length = local_read_limit(r->first, extra->range_end, r->buffer_size, r->length);
-    // whole buffers per window, at least one (the buffer itself is at most 1 GiB)
-    r->window = uint32_t(std::max<int64_t>(1, std::min<int64_t>(wbuf, kMaxBuffer / r->buffer_size)) * r->buffer_size);
     // mapped mode: verification off always (copies straight from the page cache); verified
     // reads only with HDFS3_LOCAL_MMAP=1, and only when every window starts on a page (first
     // and the window size page multiples), so windows register disjoint page ranges
     const char *mm = getenv("HDFS3_LOCAL_MMAP");
-    r->map_verified = mm && mm[0] == '1' && r->verify && r->first % kPage == 0 && r->window % kPage == 0;
+    r->map_verified = mm && mm[0] == '1' && r->verify && lay.first % kPage == 0 && lay.window % kPage == 0;
     // (a block file shorter than the block is never mapped: the pages past its end would fault, the pread fails)
-    if (r->length > 0 && !short_file && !(mm && mm[0] == '0') && (!r->verify || r->map_verified)) {
-        r->map_len = size_t((r->length + kPage - 1) / kPage * kPage);
+    if (lay.length > 0 && !short_file && !(mm && mm[0] == '0') && (!r->verify || r->map_verified)) {
+        r->map_len = size_t((lay.length + kPage - 1) / kPage * kPage);
         void *m = mmap(nullptr, r->map_len, PROT_READ, MAP_SHARED, r->data_fd, 0);
         if (m != MAP_FAILED) {
             r->map = static_cast<uint8_t *>(m);
@@ -824,14 +762,12 @@ int open_local_reader(const char *data_path, const char *meta_path, int64_t num_
             r->map_len = 0;
         }
     }
-    r->cap_data = (size_t(r->window) + 255) & ~size_t(255);
-    const size_t crc_bytes = r->verify ? 4 * ((size_t(r->window) + r->chunk_size - 1) / r->chunk_size) : 0;
     // the files are in order: whatever fails from here on is this host's
     if (extra) extra->host_fault = true;
     // the windows live on `device`, whatever the calling thread's current device is
     DeviceGuard guard(device);
     LocalResources pooled;
-    if (take_pooled(device, r->cap_data + crc_bytes, &pooled)) {
+    if (take_pooled(device, lay.arena_bytes(), &pooled)) {
         r->ctx = pooled.ctx;
         for (int i = 0; i < kSlots; ++i) r->slot[i].a = pooled.a[i];
         r->dev = pooled.dev;
@@ -840,30 +776,14 @@ int open_local_reader(const char *data_path, const char *meta_path, int64_t num_
         // the windows are pinned from a thread bound to the GPU's NUMA node (numa.h), so the
         // block file's pages are read into memory next to the GPU that DMAs them
         bool ok = true;
-        auto alloc_windows = [&] {
-            for (Window &w : r->slot) {
-                PacketArena &a = w.a;
-                if (hipHostMalloc(reinterpret_cast<void **>(&a.h), r->cap_data + crc_bytes, pinned_host_flags()) !=
-                        hipSuccess ||
-                    hipMalloc(reinterpret_cast<void **>(&a.d), r->cap_data + crc_bytes) != hipSuccess ||
-                    hipMalloc(reinterpret_cast<void **>(&a.d_res), sizeof(unsigned long long)) != hipSuccess ||
-                    hipHostMalloc(reinterpret_cast<void **>(&a.h_res), sizeof(unsigned long long),
-                                  pinned_host_flags()) != hipSuccess ||
-                    hipEventCreateWithFlags(&a.done, window_event_flags()) != hipSuccess) {
-                    ok = false;
-                    return;
-                }
-                a.cap = r->cap_data + crc_bytes;
-            }
-        };
         if (!numa_binding_enabled()) {
-            alloc_windows();  // binding off (the default): the caller's thread, under the guard
+            ok = alloc_windows(r->slot, lay.arena_bytes());  // binding off (the default): the caller's thread, under the guard
         } else {
             try {
                 std::thread([&] {
                     (void)hipSetDevice(device);
                     bind_thread_to_device(device);
-                    alloc_windows();
+                    ok = alloc_windows(r->slot, lay.arena_bytes());
                 }).join();
             } catch (const std::system_error &) {
                 ok = false;  // no thread: never let the exception cross the extern "C" entry point
@@ -873,7 +793,7 @@ int open_local_reader(const char *data_path, const char *meta_path, int64_t num_
     }
     if (int rc = hdfs3_crc_ctx_set_checksum_type(r->ctx, r->engine_type())) return bail(rc);
     for (int i = 0; i < kSlots; ++i) r->free_slots.push_back(i);
-    if (r->first < r->length) {
+    if (lay.first < lay.length) {
         r->loader = std::thread([r] { r->run_loader(); });
     } else {
         r->load_done = true;

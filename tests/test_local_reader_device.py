@@ -268,3 +268,69 @@ def test_host_and_device_reads_alternate_on_one_reader(gpu_ctx, block, staging):
         assert st["bytes_delivered"] == sum(n for _, n in dev_parts)
     finally:
         dest.free()
+
+
+def test_host_and_device_reads_agree_call_by_call(gpu_ctx, tmp_path):
+    """read() and read_dev() on the same block give the same sequence of return values up to and including
+    the first error, the same bytes, and the same answer to one more call. Chunks of 512, buffers of 4 KiB,
+    windows of two: three windows + 700 bytes is four windows (more than the three slots) and ends in a short
+    chunk. Clean, and one flipped byte in the first buffer, in the second buffer of the second window, in the
+    first chunk of the third window and in the tail chunk; opened at 0 and at 513 (buffers and windows are then
+    counted from byte 512); calls of 1000 bytes, of a window, and of the whole block."""
+    from libhdfs3_amd._native import Hdfs3CrcError
+    from libhdfs3_amd.engine import LocalBlockReader
+
+    bpc, buf, window = 512, 4096, 8192
+    n = 3 * window + 700
+    opts = dict(buffer_size=buf, window_buffers=2)
+    data = splitmix_bytes(n, 0xA9EE)
+    words = oracle_compute(data, bpc)
+
+    def calls(read, length, piece):
+        """every call's return value (an error as ("error", rc)) until an error or the end, and one call more"""
+        seq, pos, ended = [], 0, False
+        while len(seq) < 100:
+            try:
+                got = read(pos, min(piece, max(length - pos, 1)))
+            except Hdfs3CrcError as e:
+                got = ("error", e.rc, "ChecksumException" in str(e))
+            seq.append(got)
+            if ended:
+                return seq, pos
+            if isinstance(got, tuple) or got == 0:
+                ended = True
+            else:
+                pos += got
+        raise AssertionError(seq[:8])
+
+    compared = 0
+    for off in (0, 513):
+        first = off // bpc * bpc
+        flips = {"clean": None, "first_buffer": first + 500, "window1_buffer1": first + window + buf + 300,
+                 "window2_chunk0": first + 2 * window + 5, "tail_chunk": n - 3}
+        for name, where in flips.items():
+            blk = data.copy()
+            if where is not None:
+                blk[where] ^= 0x40
+            d, m = write_block(tmp_path, f"blk_{off}_{name}", blk, bpc, crc=words)
+            # the rule both reads state: nothing of the buffer, counted from `first`, that holds the bad chunk
+            good = n if where is None else first + (where // bpc * bpc - first) // buf * buf
+            want = blk[off:max(good, off)]
+            for piece in (1000, window, n):
+                host = np.full(n - off + 64, CANARY, np.uint8)
+                with LocalBlockReader(d, m, offset=off, **opts) as r:
+                    h_seq, h_pos = calls(lambda pos, k: r.read_into(host, pos, k), n - off, piece)
+                dest = Dest(gpu_ctx, n - off)
+                try:
+                    with LocalBlockReader(d, m, offset=off, **opts) as r:
+                        d_seq, d_pos = calls(lambda pos, k: r.read_into_device(dest.ptr + pos, k), n - off, piece)
+                    case = (off, name, piece)
+                    assert h_seq == d_seq, (case, h_seq[-4:], d_seq[-4:])
+                    assert h_pos == d_pos == want.nbytes, (case, h_pos, d_pos, want.nbytes)
+                    assert isinstance(h_seq[-1], tuple) == (where is not None), (case, h_seq[-4:])
+                    assert np.array_equal(host[:h_pos], want) and np.all(host[h_pos:] == CANARY), case
+                    dest.check(want)  # and canary everywhere past the count
+                    compared += 1
+                finally:
+                    dest.free()
+    assert compared == 2 * 5 * 3
