@@ -65,7 +65,6 @@ uint64_t thread_cpu_ns() {
 }
 constexpr int kMaxSlots = 64;              // deepest ring (read-ahead of a whole block)
 constexpr int32_t kMaxPacketData = 16 << 20;  // PacketReceiver.MAX_PACKET_SIZE (Hadoop)
-constexpr size_t kArenaCacheMax = 6;       // arenas a ctx keeps for its next reader
 
 struct Batch {
     PacketArena a;
@@ -127,29 +126,10 @@ int hip_err(hipError_t e, const char *what) {
     } while (0)
 
 int grow(PacketArena &a, size_t cap, size_t descs) {
-    if (cap > a.cap) {
-        if (a.h) (void)hipHostFree(a.h);
-        if (a.d) (void)hipFree(a.d);
-        a.h = a.d = nullptr;
-        a.cap = 0;
-        HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&a.h), cap, pinned_host_flags()));
-        HIP_OK(hipMalloc(reinterpret_cast<void **>(&a.d), cap));
-        a.cap = cap;
-    }
-    if (descs > a.desc_cap) {
-        if (a.h_desc) (void)hipHostFree(a.h_desc);
-        if (a.d_desc) (void)hipFree(a.d_desc);
-        a.h_desc = a.d_desc = nullptr;
-        a.desc_cap = 0;
-        HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&a.h_desc), descs * sizeof(DevSegment), pinned_host_flags()));
-        HIP_OK(hipMalloc(reinterpret_cast<void **>(&a.d_desc), descs * sizeof(DevSegment)));
-        a.desc_cap = descs;
-    }
-    if (!a.d_res) {
-        HIP_OK(hipMalloc(reinterpret_cast<void **>(&a.d_res), sizeof(unsigned long long)));
-        HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&a.h_res), sizeof(unsigned long long), pinned_host_flags()));
-        HIP_OK(hipEventCreateWithFlags(&a.done, hipEventDisableTiming | hipEventBlockingSync));
-    }
+    HIP_OK(a.buf.grow(cap, pinned_host_flags()));
+    HIP_OK(a.desc.grow(descs * sizeof(DevSegment), pinned_host_flags()));
+    HIP_OK(a.res.grow(sizeof(unsigned long long), pinned_host_flags()));
+    if (!a.done) HIP_OK(hipEventCreateWithFlags(&a.done, hipEventDisableTiming | hipEventBlockingSync));
     return 0;
 }
 
@@ -310,16 +290,16 @@ struct hdfs3_block_reader {
             if (l.pk.empty())
                 l.open(uint32_t(h.data_len), chunk_size, checksum_size, batch_packets,
                        verify && checksum_size == 4 && dense_bpc(chunk_size) && !wire_layout_forced());
-            const Placement p = l.place(uint32_t(h.data_len), crc_len, b.a.cap);
+            const Placement p = l.place(uint32_t(h.data_len), crc_len, b.a.buf.cap);
             if (p.close) {  // the header opens the next batch
                 pending_hdr = h;
                 have_pending_hdr = true;
                 break;
             }
-            if (p.need > b.a.cap)
+            if (p.need > b.a.buf.cap)
                 if (int rc = grow(b.a, p.need, size_t(batch_packets))) return rx_fail(rc, "arena growth failed");
             // the packet's checksums and data in one scatter read (:244-245 reads them as one buffer)
-            iovec v[3] = {{b.a.h + p.crc_off, crc_len}, {b.a.h + p.data_off, size_t(h.data_len)},
+            iovec v[3] = {{b.a.buf.h + p.crc_off, crc_len}, {b.a.buf.h + p.data_off, size_t(h.data_len)},
                           {next_raw, header_ahead ? sizeof(next_raw) : 0}};
             if (int rc = net::recv_fully_iov(fd, v, 3))
                 return rx_fail(rc, "RemoteBlockReader: failed to read packet payload");
@@ -329,7 +309,7 @@ struct hdfs3_block_reader {
             const int64_t ahead = std::max<int64_t>(0, recv_cursor - h.offset_in_block);
             const int64_t useful = std::max<int64_t>(0, std::min<int64_t>(h.data_len - ahead, end_offset - recv_cursor));
             l.commit(p, uint32_t(h.data_len), uint32_t(ahead), uint32_t(useful));
-            eager(b.a.h + p.data_off + ahead, useful);
+            eager(b.a.buf.h + p.data_off + ahead, useful);
             recv_cursor += h.data_len - ahead;
             if (recv_cursor >= end_offset) {
                 if (int rc = read_trailer()) return rc;
@@ -361,30 +341,26 @@ struct hdfs3_block_reader {
         LaunchEnv env = launch_env(ctx, &b.a.pieces);
         env.tables = tables;
         env.fold = ctx->d_fold_by[tables == ctx->d_tables_by[1]];
-        HIP_OK(hipMemcpyAsync(b.a.d, b.a.h, b.lay.used, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpyAsync(b.a.buf.d, b.a.buf.h, b.lay.used, hipMemcpyHostToDevice, ctx->stream));
         b.uploaded = true;
-        HIP_OK(hipMemsetAsync(b.a.d_res, 0, sizeof(unsigned long long), ctx->stream));
+        HIP_OK(hipMemsetAsync(b.a.res.d, 0, sizeof(unsigned long long), ctx->stream));
         if (b.lay.dense) {
             // one contiguous block of data_used bytes and its word array: the contiguous round kernel
             // (bpc <= 4096), the multi-round kernel or pieces + combine (R x 4096, on the batch's own
             // piece scratch); keys are the batch's chunk indices (wait() maps them to packets)
-            ChunkLaunch a{};
-            a.data = b.a.d + b.lay.d0;
-            a.len = b.lay.data_used;
-            a.bpc = chunk_size;
-            a.crc_be = b.a.d;
-            a.result = b.a.d_res;
-            a.check_short_tail = 0;  // verifyChecksum ignores a short chunk's mismatch (:319)
+            // check_short_tail 0: verifyChecksum ignores a short chunk's mismatch (:319)
+            const ChunkLaunch a = contiguous_launch(b.a.buf.d + b.lay.d0, b.lay.data_used, chunk_size, b.a.buf.d, nullptr,
+                                                    b.a.res.d, 0, /*check_short_tail=*/0, false);
             HIP_OK(launch_chunks(env, a, true));
         } else {
             const std::vector<PacketRef> &pk = b.lay.pk;
             std::vector<DevPacket> hp(pk.size());
             for (size_t i = 0; i < pk.size(); ++i) hp[i] = DevPacket{pk[i].data_off, pk[i].crc_off, pk[i].data_len, 0};
-            HIP_OK(launch_packet_batch(env, b.a.d, hp.data(), hp.size(), chunk_size, true, /*check_short_tail=*/0,
-                                       b.a.d_res, b.a.h_desc, b.a.d_desc));
+            HIP_OK(launch_packet_batch(env, b.a.buf.d, hp.data(), hp.size(), chunk_size, true, /*check_short_tail=*/0,
+                                       b.a.res.d, b.a.desc.h, b.a.desc.d));
         }
         ++ctx->launches;
-        HIP_OK(hipMemcpyAsync(b.a.h_res, b.a.d_res, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipMemcpyAsync(b.a.res.h, b.a.res.d, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(hipEventRecord(b.a.done, ctx->stream));
         return 0;
     }
@@ -398,14 +374,14 @@ struct hdfs3_block_reader {
             return rx_fail(fail(-ENOMEM, "injected pinned-memory shortage"), "arena allocation failed");
         }
 #endif
-        if (!b.a.h) {
+        if (!b.a.buf.h) {
             std::lock_guard<std::mutex> lk(ctx->arena_mu);
             if (!ctx->arena_cache.empty()) {
                 b.a = ctx->arena_cache.back();
                 ctx->arena_cache.pop_back();
             }
         }
-        if (int rc = grow(b.a, std::max(b.a.cap, ring_arena_bytes(batch_packets)), size_t(batch_packets)))
+        if (int rc = grow(b.a, std::max(b.a.buf.cap, ring_arena_bytes(batch_packets)), size_t(batch_packets)))
             return rx_fail(rc, "arena allocation failed");
         return 0;
     }
@@ -477,7 +453,7 @@ struct hdfs3_block_reader {
     int wait(Batch &b) {
         if (b.verified) return 0;
         if (int rc = wait_event(b.a.done)) return rc;
-        if (const unsigned long long r = *b.a.h_res) b.bad_pkt = b.lay.bad_packet(r);
+        if (const unsigned long long r = *b.a.res.h) b.bad_pkt = b.lay.bad_packet(r);
         b.verified = true;
         return 0;
     }
@@ -548,9 +524,9 @@ struct hdfs3_block_reader {
                     if (dest && out + total == dest + delivered)
                         ;  // the receiver already put these bytes here
                     else if (copy_nt && pc.n >= 4096)
-                        memcpy_stream(out + total, b.a.h + pc.src, pc.n);
+                        memcpy_stream(out + total, b.a.buf.h + pc.src, pc.n);
                     else
-                        std::memcpy(out + total, b.a.h + pc.src, pc.n);
+                        std::memcpy(out + total, b.a.buf.h + pc.src, pc.n);
                     total += int32_t(pc.n);
                     delivered += int64_t(pc.n);
                 }
@@ -570,12 +546,8 @@ struct hdfs3_block_reader {
         if (error) return fail(error, "%s", error_msg.c_str());
         if (len <= 0 || !d_out) return fail(-EINVAL, "invalid read buffer");
         DeviceGuard guard(ctx->device);
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, d_out) != hipSuccess || at.type != hipMemoryTypeDevice ||
-            at.device != ctx->device) {
-            (void)hipGetLastError();  // a host pointer is the caller's mistake, not a fault of the GPU
+        if (!is_device_memory_of(ctx, d_out))
             return fail(-EINVAL, "read_dev: the buffer is not device memory of device %d", ctx->device);
-        }
         if (!dev_done) HIP_OK(hipEventCreateWithFlags(&dev_done, hipEventDisableTiming | hipEventBlockingSync));
         int32_t total = 0;
         int failed = 0;         // the call ends with this error once its gathers completed
@@ -620,12 +592,14 @@ struct hdfs3_block_reader {
                     // against the upload: such a batch's copies are waited for before it goes back.
                     const bool own_upload = !b.uploaded;
                     if (own_upload) {
-                        const hipError_t e = hipMemcpyAsync(b.a.d, b.a.h, b.lay.used, hipMemcpyHostToDevice, ctx->stream);
+                        const hipError_t e =
+                            hipMemcpyAsync(b.a.buf.d, b.a.buf.h, b.lay.used, hipMemcpyHostToDevice, ctx->stream);
                         if (e != hipSuccess) rc = hip_err(e, "hipMemcpyAsync");
                         b.uploaded = true;
                     }
                     unsigned launched = 0;
-                    if (!rc) rc = gather_dev(ctx, d_out, size_t(len), b.a.d, b.lay.used, rg.data(), rg.size(), &launched);
+                    if (!rc)
+                        rc = gather_dev(ctx, d_out, size_t(len), b.a.buf.d, b.lay.used, rg.data(), rg.size(), &launched);
                     enqueued = true;
                     if (!rc && own_upload) rc = complete();
                     dev_launches.fetch_add(launched, std::memory_order_relaxed);
@@ -674,9 +648,9 @@ struct hdfs3_block_reader {
         for (int i = 0; i < kPhases; ++i) g_phase_ns[i].fetch_add(t_ns[i].load(), std::memory_order_relaxed);
         // a borrowed ctx keeps up to a ring's worth of arenas for its next reader (a read-ahead
         // reader's deep ring included: the stream's next read-ahead takes them back)
-        const size_t cache_max = std::max(kArenaCacheMax, slot.size());
+        const size_t cache_max = std::max(kArenaCacheKeep, slot.size());
         for (Batch &b : slot) {
-            if (!b.a.h) continue;
+            if (!b.a.buf.h) continue;
             bool cached = false;
             if (ctx && !own_ctx) {
                 std::lock_guard<std::mutex> lk(ctx->arena_mu);

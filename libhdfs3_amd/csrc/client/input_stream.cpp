@@ -37,7 +37,6 @@ using namespace hdfs3crc;
 namespace {
 
 constexpr int64_t kMaxSkip = 128 * 1024;  // InputStreamImpl.cpp:1146
-constexpr int kShallowArenas = 6;  // arenas any pooled ctx keeps (hdfs3_crc.cpp kArenaCacheKeep)
 
 struct Node {
     std::string host;
@@ -199,7 +198,7 @@ struct hdfs3_input_stream {
             // every shallow pooled ctx keeps (the stream's own on-demand reader's among them)
             const int64_t arena = block_reader_arena_bytes(&opts);
             const int64_t cap = int64_t(pool_pinned_cap_bytes());
-            const int64_t fit = std::max<int64_t>(0, cap - int64_t(kShallowArenas) * arena) /
+            const int64_t fit = std::max<int64_t>(0, cap - int64_t(kArenaCacheKeep) * arena) /
                                 int64_t(ahead_blocks + 1) / arena;
             const int slots = int(std::max<int64_t>(3, std::min<int64_t>({(want + unit - 1) / unit + 1, 64, fit})));
             hdfs3_crc_ctx *c = nullptr;

@@ -118,7 +118,7 @@ constexpr size_t kPoolMax = 16;
 bool take_pooled(int device, size_t cap, LocalResources *out) {
     std::lock_guard<std::mutex> lk(g_pool_mu);
     for (size_t i = 0; i < g_pool.size(); ++i) {
-        if (g_pool[i].ctx->device == device && g_pool[i].a[0].cap >= cap) {
+        if (g_pool[i].ctx->device == device && g_pool[i].a[0].buf.cap >= cap) {
             *out = g_pool[i];
             g_pool.erase(g_pool.begin() + long(i));
             return true;
@@ -142,9 +142,8 @@ LocalPoolStats entry_bytes(const LocalResources &r) {
     LocalPoolStats st;
     ctx_footprint(r.ctx, &st.pinned, &st.device);
     for (const PacketArena &a : r.a) {
-        const uint64_t n = a.cap + (a.h_res ? sizeof(unsigned long long) : 0);
-        st.pinned += n;
-        st.device += n;
+        st.pinned += a.pinned_bytes();
+        st.device += a.device_bytes();
     }
     if (r.dev.d_gate) st.device += 2 * sizeof(uint64_t);
     if (r.dev.h_gate) st.pinned += sizeof(unsigned long long);
@@ -192,7 +191,7 @@ struct Window {
     LocalWindow g;            // its bytes of the block, its chunks and their .meta words
     int64_t bad_chunk = -1;   // first mismatching chunk (block-relative), after wait
     bool verified = false;
-    const uint8_t *src = nullptr;  // where read() copies from: a.h, or the mapping
+    const uint8_t *src = nullptr;  // where read() copies from: a.buf.h, or the mapping
     void *reg = nullptr;           // mapped mode: the window's registered page range
 };
 
@@ -310,9 +309,9 @@ struct hdfs3_local_reader {
         const size_t cap_data = lay.cap_data;
         w.bad_chunk = -1;
         w.verified = false;
-        w.src = w.a.h;
+        w.src = w.a.buf.h;
         w.reg = nullptr;
-        const uint8_t *h2d_src = w.a.h;
+        const uint8_t *h2d_src = w.a.buf.h;
         if (map && !verify) {
             w.src = map + start;  // no staging at all: read() copies from the page cache
         } else if (map && map_verified && start % kPage == 0) {
@@ -327,8 +326,8 @@ struct hdfs3_local_reader {
                 (void)hipGetLastError();  // pread path for this window
             }
         }
-        if (w.src == w.a.h) {
-            if (int rc = CopyPool::get().pread(data_fd, w.a.h, len, start)) {
+        if (w.src == w.a.buf.h) {
+            if (int rc = CopyPool::get().pread(data_fd, w.a.buf.h, len, start)) {
                 load_msg = "LocalBlockReader: failed to read the block file";
                 replica_fault = true;
                 return rc;
@@ -339,20 +338,21 @@ struct hdfs3_local_reader {
             w.verified = true;
             return 0;
         }
-        if (int rc = pread_fully(meta_fd, w.a.h + cap_data, w.g.meta_bytes, w.g.meta_off)) {
+        if (int rc = pread_fully(meta_fd, w.a.buf.h + cap_data, w.g.meta_bytes, w.g.meta_off)) {
             load_msg = "LocalBlockReader: failed to read the meta file";
             replica_fault = true;
             return rc;
         }
-        HIP_OK(hipMemcpyAsync(w.a.d, h2d_src, len, hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipMemcpyAsync(w.a.d + cap_data, w.a.h + cap_data, w.g.meta_bytes, hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipMemsetAsync(w.a.d_res, 0, sizeof(unsigned long long), ctx->stream));
-        if (int rc = hdfs3_crc32c_verify_dev_async(ctx, w.a.d, len, chunk_size, w.a.d + cap_data,
-                                                   /*check_short_tail=*/1, reinterpret_cast<uint64_t *>(w.a.d_res))) {
+        HIP_OK(hipMemcpyAsync(w.a.buf.d, h2d_src, len, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpyAsync(w.a.buf.d + cap_data, w.a.buf.h + cap_data, w.g.meta_bytes, hipMemcpyHostToDevice,
+                              ctx->stream));
+        HIP_OK(hipMemsetAsync(w.a.res.d, 0, sizeof(unsigned long long), ctx->stream));
+        if (int rc = hdfs3_crc32c_verify_dev_async(ctx, w.a.buf.d, len, chunk_size, w.a.buf.d + cap_data,
+                                                   /*check_short_tail=*/1, reinterpret_cast<uint64_t *>(w.a.res.d))) {
             load_msg = hdfs3_crc_last_error();
             return rc;
         }
-        HIP_OK(hipMemcpyAsync(w.a.h_res, w.a.d_res, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipMemcpyAsync(w.a.res.h, w.a.res.d, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(hipEventRecord(w.a.done, ctx->stream));
         return 0;
     }
@@ -402,7 +402,7 @@ struct hdfs3_local_reader {
     int wait(Window &w) {
         if (w.verified) return 0;
         HIP_OK(hipEventSynchronize(w.a.done));
-        const unsigned long long r = *w.a.h_res;
+        const unsigned long long r = *w.a.res.h;
         if (r) w.bad_chunk = int64_t(w.g.chunk0) + hdfs3_crc_decode_result(r);
         w.verified = true;
         return 0;
@@ -487,7 +487,7 @@ struct hdfs3_local_reader {
 
     // ---- read() into device memory ----------------------------------------------------------
     // Verification on: a window's bytes are already in HBM (load() uploaded them for the verify), so they go
-    // from w.a.d to d_out in one guarded delivery per window (deliver_dev: the kernel reads the window's result
+    // from w.a.buf.d to d_out in one guarded delivery per window (deliver_dev: the kernel reads the window's result
     // word itself and copies only what it allows). The caller's thread does not wait for a window's result
     // before it enqueues: it waits for a window's `done` event only when it has nothing left to enqueue, to
     // give the slot back (the loader's next pread overwrites the PINNED window, which no stream orders against
@@ -520,12 +520,8 @@ struct hdfs3_local_reader {
         if (error) return fail(error, "%s", error_msg.c_str());
         if (!d_out || len <= 0) return fail(-EINVAL, "invalid read buffer");
         DeviceGuard guard(ctx->device);
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, d_out) != hipSuccess || at.type != hipMemoryTypeDevice ||
-            at.device != ctx->device) {
-            (void)hipGetLastError();  // a host pointer is the caller's mistake, not a fault of the GPU
+        if (!is_device_memory_of(ctx, d_out))
             return fail(-EINVAL, "read_dev: the buffer is not device memory of device %d", ctx->device);
-        }
         if (cursor >= lay.length) return 0;
         if (int rc = ensure_device_words()) return sticky(rc, std::string(hdfs3_crc_last_error()));
         return verify ? read_dev_verified(d_out, len) : read_dev_plain(d_out, len);
@@ -597,7 +593,7 @@ struct hdfs3_local_reader {
             const LocalSpan sp = LocalLayout::span(w.g, pos, len - (pos - from), end);
             if (sp.n > 0) {
                 const CopyRange rg{uint64_t(sp.begin - w.g.start), uint64_t(sp.begin - from), uint64_t(sp.n)};
-                const DeliverGuard g{reinterpret_cast<const uint64_t *>(w.a.d_res),
+                const DeliverGuard g{reinterpret_cast<const uint64_t *>(w.a.res.d),
                                      known_bad ? nullptr : dev.d_gate + gate_cur,
                                      known_bad ? nullptr : dev.d_gate + (gate_cur ^ 1),
                                      0,
@@ -605,7 +601,7 @@ struct hdfs3_local_reader {
                                      uint64_t(lay.buffer_size),
                                      chunk_size};
                 unsigned launched = 0;
-                const int rc = deliver_dev(ctx, d_out, size_t(len), w.a.d, w.g.len, &rg, 1, g, &launched);
+                const int rc = deliver_dev(ctx, d_out, size_t(len), w.a.buf.d, w.g.len, &rg, 1, g, &launched);
                 dev_launches.fetch_add(launched, std::memory_order_relaxed);
                 if (rc) return sticky(rc, std::string(hdfs3_crc_last_error()));  // nothing is known to be in place
                 enqueued = true;
@@ -702,13 +698,10 @@ int local_opts_check(const hdfs3_local_opts *opts) {
 static bool alloc_windows(Window (&slot)[kSlots], size_t bytes) {
     for (Window &w : slot) {
         PacketArena &a = w.a;
-        if (hipHostMalloc(reinterpret_cast<void **>(&a.h), bytes, pinned_host_flags()) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&a.d), bytes) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&a.d_res), sizeof(unsigned long long)) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void **>(&a.h_res), sizeof(unsigned long long), pinned_host_flags()) != hipSuccess ||
+        if (a.buf.grow(bytes, pinned_host_flags()) != hipSuccess ||
+            a.res.grow(sizeof(unsigned long long), pinned_host_flags()) != hipSuccess ||
             hipEventCreateWithFlags(&a.done, window_event_flags()) != hipSuccess)
             return false;
-        a.cap = bytes;
     }
     return true;
 }

@@ -158,13 +158,8 @@ struct hdfs3_output_stream {
         chunk_cur = bpc;
         cpp_cur = chunks_per_packet;
         for (WBatch &b : batch) {
-            HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&b.a.h), arena_bytes, hipHostMallocDefault));
-            HIP_OK(hipMalloc(reinterpret_cast<void **>(&b.a.d), arena_bytes));
-            b.a.cap = arena_bytes;
-            HIP_OK(hipHostMalloc(reinterpret_cast<void **>(&b.a.h_desc), batch_packets * sizeof(DevSegment),
-                                 hipHostMallocDefault));
-            HIP_OK(hipMalloc(reinterpret_cast<void **>(&b.a.d_desc), batch_packets * sizeof(DevSegment)));
-            b.a.desc_cap = size_t(batch_packets);
+            HIP_OK(b.a.buf.grow(arena_bytes, hipHostMallocDefault));
+            HIP_OK(b.a.desc.grow(batch_packets * sizeof(DevSegment), hipHostMallocDefault));
             HIP_OK(hipEventCreateWithFlags(&b.a.done, hipEventDisableTiming));
             b.pk.reserve(size_t(batch_packets));
         }
@@ -177,7 +172,7 @@ struct hdfs3_output_stream {
     int place_pending() {
         if (dev_pending.empty()) return 0;
         unsigned launched = 0;
-        const int rc = gather_dev(ctx, batch[cur_batch].a.d, crc_region, dev_src, dev_src_len, dev_pending.data(),
+        const int rc = gather_dev(ctx, batch[cur_batch].a.buf.d, crc_region, dev_src, dev_src_len, dev_pending.data(),
                                   dev_pending.size(), &launched);
         dev_pending.clear();
         dev_launches += launched;
@@ -213,22 +208,22 @@ struct hdfs3_output_stream {
         b.chunks = chunks;
         if (n) {
             if (!b.ledger.any_device()) {
-                HIP_OK(hipMemcpyAsync(b.a.d + lo, b.a.h + lo, hi - lo, hipMemcpyHostToDevice, ctx->stream));
+                HIP_OK(hipMemcpyAsync(b.a.buf.d + lo, b.a.buf.h + lo, hi - lo, hipMemcpyHostToDevice, ctx->stream));
             } else {  // around the placed bytes, which the host arena does not hold
                 b.ledger.uploads(&span);
                 for (const ByteRange &r : span)
-                    HIP_OK(hipMemcpyAsync(b.a.d + r.off, b.a.h + r.off, r.len, hipMemcpyHostToDevice, ctx->stream));
+                    HIP_OK(hipMemcpyAsync(b.a.buf.d + r.off, b.a.buf.h + r.off, r.len, hipMemcpyHostToDevice, ctx->stream));
             }
             // the batch's own piece scratch (bpc = R x 4096 batches of whole-round packets: pieces + combine)
-            HIP_OK(launch_packet_batch(launch_env(ctx, &b.a.pieces), b.a.d, hp, n, bpc, false, 0, nullptr, b.a.h_desc,
-                                       b.a.d_desc));
+            HIP_OK(launch_packet_batch(launch_env(ctx, &b.a.pieces), b.a.buf.d, hp, n, bpc, false, 0, nullptr, b.a.desc.h,
+                                       b.a.desc.d));
             ++ctx->launches;
             if (b.ledger.any_device()) {  // the sink is handed host packets
                 b.ledger.downloads(&span);
                 for (const ByteRange &r : span)
-                    HIP_OK(hipMemcpyAsync(b.a.h + r.off, b.a.d + r.off, r.len, hipMemcpyDeviceToHost, ctx->stream));
+                    HIP_OK(hipMemcpyAsync(b.a.buf.h + r.off, b.a.buf.d + r.off, r.len, hipMemcpyDeviceToHost, ctx->stream));
             }
-            HIP_OK(hipMemcpyAsync(b.a.h + crc_region, b.a.d + crc_region, 4 * chunks, hipMemcpyDeviceToHost,
+            HIP_OK(hipMemcpyAsync(b.a.buf.h + crc_region, b.a.buf.d + crc_region, 4 * chunks, hipMemcpyDeviceToHost,
                                   ctx->stream));
         }
         HIP_OK(hipEventRecord(b.a.done, ctx->stream));
@@ -239,10 +234,10 @@ struct hdfs3_output_stream {
     int emit(WBatch &b) {
         if (!b.dispatched) return 0;
         HIP_OK(hipEventSynchronize(b.a.done));
-        const uint8_t *words = b.a.h + crc_region;
+        const uint8_t *words = b.a.buf.h + crc_region;
         for (const Pkt &p : b.pk) {
             const uint32_t nch = (p.data_len + bpc - 1) / bpc;
-            uint8_t *sums = b.a.h + p.data_off - 4ull * nch;
+            uint8_t *sums = b.a.buf.h + p.data_off - 4ull * nch;
             std::memcpy(sums, words, 4ull * nch);  // already big-endian (Packet::addChecksum)
             words += 4ull * nch;
             wire::PacketHeader h;
@@ -293,7 +288,7 @@ struct hdfs3_output_stream {
         p->seqno = next_seqno++;
         p->block_index = block_index;
         if (position) {  // the flushed partial chunk opens the new packet again
-            std::memcpy(batch[cur_batch].a.h + p->data_off, carry.data(), position);
+            std::memcpy(batch[cur_batch].a.buf.h + p->data_off, carry.data(), position);
             batch[cur_batch].ledger.host(p->data_off, position);
             p->data_len = position;
         }
@@ -304,7 +299,7 @@ struct hdfs3_output_stream {
     // sendPacket: the packet is complete; it leaves with its batch
     void send_current() {
         pipeline_open = true;
-        if (position && cur) carry_from = batch[cur_batch].a.h + cur->data_off + cur->data_len - position;
+        if (position && cur) carry_from = batch[cur_batch].a.buf.h + cur->data_off + cur->data_len - position;
         cur = nullptr;
     }
 
@@ -357,7 +352,7 @@ struct hdfs3_output_stream {
                 dev_pending.push_back(CopyRange{uint64_t(size - todo), at, n});
                 batch[cur_batch].ledger.device(at, n);
             } else {
-                std::memcpy(batch[cur_batch].a.h + at, buf + (size - todo), n);
+                std::memcpy(batch[cur_batch].a.buf.h + at, buf + (size - todo), n);
                 batch[cur_batch].ledger.host(at, n);
             }
             cur->data_len += n;
@@ -517,13 +512,9 @@ int32_t hdfs3_output_write_dev(hdfs3_output_stream *s, const void *d_buf, int32_
     if (!s || !d_buf || len <= 0) return posix_fail(EINVAL, "hdfs3_output_write_dev: invalid argument");
     if (s->error) return posix_fail(EIO, s->error_msg);
     DeviceGuard g(s->ctx->device);
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, d_buf) != hipSuccess || at.type != hipMemoryTypeDevice ||
-        at.device != s->ctx->device) {
-        (void)hipGetLastError();  // a host pointer is the caller's mistake, not a fault of the GPU
+    if (!is_device_memory_of(s->ctx, d_buf))
         return posix_fail(EINVAL, "hdfs3_output_write_dev: the buffer is not device memory of device " +
                                       std::to_string(s->ctx->device));
-    }
     if (!s->dev_done) {
         const hipError_t e = hipEventCreateWithFlags(&s->dev_done, hipEventDisableTiming);
         if (e != hipSuccess) return posix_fail(EIO, std::string("hipEventCreateWithFlags: ") + hipGetErrorString(e));

@@ -99,7 +99,11 @@ struct BatchLayout {
 
     // A non-zero verify result word -> the batch's first bad packet
     int64_t bad_packet(unsigned long long r) const {
-        if (!dense) return int64_t((~r) >> 32);
+        if (!dense) {
+            int64_t pkt = -1;
+            split_result_key(r, &pkt, nullptr);
+            return pkt;
+        }
         const uint64_t chunk = ~r;  // the first bad chunk of the batch
         return int64_t(std::upper_bound(chunk0.begin(), chunk0.end(), chunk) - chunk0.begin()) - 1;
     }

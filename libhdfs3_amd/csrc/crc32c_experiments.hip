@@ -4,7 +4,11 @@
 // Bit-exact variants are parity-tested (tests/test_gpu_parity.py); the diagnostic one gives
 // wrong results on purpose. The designs that lost their A/B were removed in round 3; their
 // numbers stay in docs/DESIGN_HISTORY.md §5 and profiles/.
+#include <cerrno>
+
 #include "crc32c_wave.h"
+#include "ctx.h"
+#include "hdfs3_crc.h"
 
 namespace hdfs3crc {
 namespace {
@@ -161,3 +165,56 @@ hipError_t launch_lane_read(const uint8_t *d, uint64_t len, uint32_t bpc, uint32
 }
 
 }  // namespace hdfs3crc
+
+// ---- measurement hooks (bench.py's read ceiling, tools/, the A/B tests). Not part of hdfs3_crc.h;
+// like the rest of this file they exist in libhdfs3_crc_lab.so only. ----
+using namespace hdfs3crc;
+
+extern "C" {
+
+// Coalesced read-only stream over [d, d+len): the achievable HBM read ceiling.
+int hdfs3x_stream_read_ex(hdfs3_crc_ctx *ctx, const void *d, size_t len, int grid, void *d_sink, uint32_t flags);
+int hdfs3x_stream_read(hdfs3_crc_ctx *ctx, const void *d, size_t len, int grid, void *d_sink) {
+    return hdfs3x_stream_read_ex(ctx, d, len, grid, d_sink, 0);
+}
+
+// flags: HDFS3_LAUNCH_OVERLAP_PREVIOUS, for the same-shape ceiling of overlapped verifies
+int hdfs3x_stream_read_ex(hdfs3_crc_ctx *ctx, const void *d, size_t len, int grid, void *d_sink, uint32_t flags) {
+    if (!ctx) return fail(-EINVAL, "null ctx");
+    DeviceGuard g(ctx->device);
+    HIP_TRY(launch_stream_read(static_cast<const uint8_t *>(d), len, static_cast<uint32_t *>(d_sink),
+                               grid != 0 ? grid : ctx->grid_cap * 8, ctx->stream,
+                               (flags & HDFS3_LAUNCH_OVERLAP_PREVIOUS) != 0));
+    return 0;
+}
+
+// The CRC kernel's chunk-per-lane access pattern without the table arithmetic.
+int hdfs3x_lane_read(hdfs3_crc_ctx *ctx, const void *d, size_t len, uint32_t bpc, void *d_sink) {
+    if (!ctx) return fail(-EINVAL, "null ctx");
+    DeviceGuard g(ctx->device);
+    HIP_TRY(launch_lane_read(static_cast<const uint8_t *>(d), len, bpc, static_cast<uint32_t *>(d_sink),
+                             ctx->grid_cap, ctx->stream));
+    return 0;
+}
+
+int hdfs3x_grid_cap(hdfs3_crc_ctx *ctx) { return ctx ? ctx->grid_cap : 0; }
+
+// Process-wide kernel-variant knob for in-process A/B measurements (tools/ab.py).
+void hdfs3x_set_variant(int v) { set_variant(v); }
+
+// Clock stamps of variant 125 and the stream-read kernel (tools/clock_ramp.py): installs a device
+// buffer of cap x 4 u64 ({s_memtime, s_memrealtime} at workgroup 0's start and end, one slot per
+// launch); returns the number of stamps written into the previous buffer, or a negative errno.
+int hdfs3x_clock_stamps(void *d_buf, unsigned int cap) {
+    unsigned int n = 0;
+    HIP_TRY(lab_clock_buffer(static_cast<unsigned long long *>(d_buf), cap, &n));
+    return int(n);
+}
+
+int hdfs3x_wave_stamps(void *d_buf, unsigned int cap) {
+    unsigned int n = 0;
+    HIP_TRY(lab_wave_buffer(static_cast<unsigned long long *>(d_buf), cap, &n));
+    return int(n);
+}
+
+}  // extern "C"

@@ -46,6 +46,24 @@ struct ChunkLaunch {
 // lab clock stamps: launches numbered by the host (kernel argument), see LabClock
 inline std::atomic<uint32_t> g_lab_seq{0};
 
+// The launch over one contiguous run of chunks: verify reads crc_in and reports into *result with
+// chunk_base added to its chunk indices, compute writes crc_out
+inline ChunkLaunch contiguous_launch(const void *data, uint64_t len, uint32_t bpc, const void *crc_in, void *crc_out,
+                                     unsigned long long *result, uint64_t chunk_base, int check_short_tail,
+                                     bool overlap) {
+    ChunkLaunch a{};
+    a.data = static_cast<const uint8_t *>(data);
+    a.len = len;
+    a.bpc = bpc;
+    a.crc_be = static_cast<const uint8_t *>(crc_in);
+    a.out_be = static_cast<uint8_t *>(crc_out);
+    a.result = result;
+    a.chunk_base = chunk_base;
+    a.check_short_tail = check_short_tail;
+    a.overlap_previous = overlap;
+    return a;
+}
+
 // The launch of a planned pitch stream whose first packet's data and words are at data / crc
 inline ChunkLaunch pitch_stream_launch(const PitchStream &s, const uint8_t *data, uint8_t *crc, uint32_t bpc,
                                        int check_short_tail, unsigned long long *result) {

@@ -1,5 +1,6 @@
-// Internal: the hdfs3_crc_ctx definition, shared by the C-ABI (hdfs3_crc.cpp) and the
-// block reader (client/block_reader.cpp). Not installed.
+// Internal: the hdfs3_crc_ctx definition and what its owners share. ctx.cpp: the error slot, the table
+// images, a ctx's life cycle and settings; ctx_pool.cpp: the process-wide pool and its pinned budget;
+// hdfs3_crc.cpp: the C entry points that launch; client/: the readers and streams. Not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +17,16 @@ namespace hdfs3crc {
 
 // Sets the thread-local message returned by hdfs3_crc_last_error(); returns `code`.
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// The ABI layer's mapping of a HIP error (ctx.cpp, hdfs3_crc.cpp, the lab hooks): -ENOMEM,
+// -EINVAL, -ENODEV or -EIO, the message "<what>: <HIP's text>". The readers and streams of client/ keep
+// mappings of their own.
+int hip_fail(hipError_t e, const char *what);
+#define HIP_TRY(expr)                                               \
+    do {                                                            \
+        hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return hdfs3crc::hip_fail(e_, #expr); \
+    } while (0)
 
 // Makes `dev` the calling thread's current device for the guard's lifetime (hipMalloc,
 // hipHostMalloc and event creation act on the current device).
@@ -35,25 +46,57 @@ struct DeviceGuard {
 // Staging segment of the host-buffer API: 16 MiB of payload per H2D transfer.
 constexpr size_t kSegmentBytes = 16u << 20;
 
+// Cached arenas any pooled ctx keeps for its next reader (ctx_release, the block reader's close), and
+// what an input stream's read-ahead budget leaves for such contexts
+constexpr size_t kArenaCacheKeep = 6;
+
+// A pinned host buffer and its device mirror, owned together. `cap` (bytes of each) is set only once
+// both exist: after a failed grow whatever was allocated is freed by the next grow or release.
+// The owner picks the host flags (numa.h pinned_host_flags() or hipHostMallocDefault).
+template <class T = uint8_t>
+struct Mirror {
+    T *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+
+    hipError_t grow(size_t bytes, unsigned host_flags) {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        if (hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&h), bytes, host_flags); e != hipSuccess) return e;
+        if (hipError_t e = hipMalloc(reinterpret_cast<void **>(&d), bytes); e != hipSuccess) return e;
+        cap = bytes;
+        return hipSuccess;
+    }
+    void release() {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        h = d = nullptr;
+        cap = 0;
+    }
+    size_t bytes() const { return cap; }
+};
+
 struct Slot {
-    uint8_t *h_data = nullptr, *h_crc = nullptr;  // pinned
-    uint8_t *d_data = nullptr, *d_crc = nullptr;  // device
-    size_t data_cap = 0, crc_cap = 0;
+    Mirror<> data, crc;
     hipEvent_t done = nullptr;
-    // compute: CRC bytes waiting in h_crc to be copied out once `done` fires
+    // compute: CRC bytes waiting in crc.h to be copied out once `done` fires
     uint8_t *pending_out = nullptr;
     size_t pending_bytes = 0;
+
+    void release() {  // the buffers only: the event stays for the slot's next use
+        data.release();
+        crc.release();
+    }
+    uint64_t pinned_bytes() const { return data.bytes() + crc.bytes(); }
+    uint64_t device_bytes() const { return pinned_bytes(); }
 };
 
 // One packet batch's buffers for the block reader: pinned wire arena + its HBM mirror,
 // packet descriptors, the verify result word and the completion event. Cached in the ctx
 // so the block readers an input stream opens one after another reuse them.
 struct PacketArena {
-    uint8_t *h = nullptr, *d = nullptr;
-    size_t cap = 0;
-    DevSegment *h_desc = nullptr, *d_desc = nullptr;  // descriptor staging (DevSegment-sized)
-    size_t desc_cap = 0;
-    unsigned long long *d_res = nullptr, *h_res = nullptr;
+    Mirror<> buf;
+    Mirror<DevSegment> desc;         // descriptor staging
+    Mirror<unsigned long long> res;  // the verify result word
     hipEvent_t done = nullptr;
     // 4096-byte piece CRCs of a batch at bpc = R x 4096 (launch_chunks' pieces + combine): the
     // batch's own, so two readers verifying on one ctx (a stream's sequential reader and a pread's)
@@ -62,15 +105,15 @@ struct PacketArena {
 
     void release() {
         pieces.release();
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        if (h_desc) (void)hipHostFree(h_desc);
-        if (d_desc) (void)hipFree(d_desc);
-        if (h_res) (void)hipHostFree(h_res);
-        if (d_res) (void)hipFree(d_res);
+        buf.release();
+        desc.release();
+        res.release();
         if (done) (void)hipEventDestroy(done);
         *this = PacketArena();
     }
+    uint64_t pinned_bytes() const { return buf.bytes() + desc.bytes() + res.bytes(); }
+    // the arena's own piece scratch (bpc = R x 4096 batches) stays allocated while it is cached
+    uint64_t device_bytes() const { return pinned_bytes() + pieces.cap[0] + pieces.cap[1]; }
 };
 
 }  // namespace hdfs3crc
@@ -119,15 +162,15 @@ struct hdfs3_crc_ctx {
     uint32_t *d_fold_by[2] = {nullptr, nullptr};
     int checksum_type = 2;
     uint32_t poly = 0x82F63B78u;        // reflected polynomial of checksum_type
-    unsigned long long *d_result = nullptr;
-    unsigned long long *h_result = nullptr;  // pinned
+    hdfs3crc::Mirror<unsigned long long> result;  // the blocking calls' verdict word
     // blocks API: a ring of descriptor stagings, each reusable once its event fired
     struct SegStage {
-        hdfs3crc::DevSegment *h = nullptr, *d = nullptr;
-        size_t cap = 0;
+        hdfs3crc::Mirror<hdfs3crc::DevSegment> seg;
         hipEvent_t done = nullptr;
-        bool armed = false;  // done recorded after a copy out of h that may still be pending
+        bool armed = false;  // done recorded after a copy out of seg.h that may still be pending
         hipEvent_t copied = nullptr;  // the descriptors' copy on desc_stream (DescCopy)
+        uint64_t pinned_bytes() const { return seg.bytes(); }
+        uint64_t device_bytes() const { return seg.bytes(); }
     } seg_ring[4];
     // long descriptor lists copy on this stream, beside the previous launch (DescCopy; created on first use)
     hipStream_t desc_stream = nullptr;
@@ -142,6 +185,14 @@ struct hdfs3_crc_ctx {
 };
 
 namespace hdfs3crc {
+// Makes `type` (HDFS3_CHECKSUM_TYPE_CRC32C or _CRC32, checked by the caller) the ctx's polynomial: its
+// table and fold images and `poly`
+void select_checksum_type(hdfs3_crc_ctx *ctx, int type);
+// device bytes of a ctx's table and fold images, both polynomials
+uint64_t table_image_bytes();
+// true when p is device memory of the ctx's device. Anything else (a host pointer is the caller's mistake,
+// not a fault of the GPU) clears HIP's sticky error and gives false; the caller words its own error.
+bool is_device_memory_of(hdfs3_crc_ctx *ctx, const void *p);
 // A ctx's launch environment. own_pieces: a batch arena's piece scratch (block reader, output stream), whose
 // launches may come from another thread and so leave the ctx's own word and piece scratch alone
 inline LaunchEnv launch_env(hdfs3_crc_ctx *ctx, PieceScratch *own_pieces = nullptr) {

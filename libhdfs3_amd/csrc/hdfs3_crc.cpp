@@ -1,9 +1,6 @@
-// C-ABI of the MI355X CRC32C engine (include/hdfs3_crc.h).
-//
-// Error convention mirrors libhdfs3's C API (src/client/Hdfs.cpp:75-80,243-327):
-// no exception crosses extern "C"; failures return a negative errno code and
-// leave a thread-local message (hdfs3_crc_last_error, cf. hdfsGetLastError at
-// Hdfs.cpp:59,329).
+// C-ABI of the MI355X CRC32C engine (include/hdfs3_crc.h): the entry points that launch. The ctx itself
+// is ctx.cpp's, the pool of contexts ctx_pool.cpp's; errors follow ctx.cpp's convention (a negative
+// errno code and hdfs3_crc_last_error).
 #include "hdfs3_crc.h"
 #include "md5.h"
 
@@ -12,13 +9,8 @@
 #include <algorithm>
 #include <cerrno>
 #include <cstddef>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
-#include <mutex>
-#include <new>
 
 #include "copy_pool.h"
 #include "crc32c_kernels.h"
@@ -33,80 +25,6 @@ uint32_t host_update(uint32_t state, const void *p, size_t n);
 
 using namespace hdfs3crc;
 
-namespace hdfs3crc {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-}  // namespace hdfs3crc
-
-namespace hdfs3crc {
-
-// Per polynomial ([0] CRC32C, [1] CRC32): slice tables, then the fold image (kFoldWords
-// matrix columns, then the 4 affine nibble-table sets for G = 8, 16, 32, 64 of the round
-// kernel), built once per process.
-// the device copy: the product stops before the lab-only sets
-#if HDFS3_LAB
-constexpr size_t kFoldUploadBytes = sizeof(uint32_t) * kFoldImageWords;
-#else
-constexpr size_t kFoldUploadBytes = sizeof(uint32_t) * kFoldAffineOldOff;
-#endif
-
-struct HostImage {
-    uint32_t t[kSlices][kTableEntries];
-    uint32_t fold[kFoldImageWords];
-};
-
-const HostImage *host_images() {
-    static HostImage img[2];
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const uint32_t polys[2] = {kPolyReflected, kPolyCrc32};
-        for (int p = 0; p < 2; ++p) {
-            build_slice_tables(img[p].t, polys[p]);
-            build_fold_matrices(img[p].t[0], img[p].fold);
-            for (int set = 0; set < 4; ++set) {
-                uint32_t *nib = img[p].fold + kFoldAffineOff + set * kFoldNibbleWords;
-                build_fold_nibbles_pre(img[p].t[0], img[p].fold, set, nib);
-                build_fold_affine(img[p].t[0], set, nib);
-#if HDFS3_LAB  // the round-4 sets of lab variant 157; the product never reads them (nor uploads them)
-                uint32_t *old = img[p].fold + kFoldAffineOldOff + set * kFoldNibbleWords;
-                build_fold_nibbles(img[p].fold, set, old);
-                build_fold_affine(img[p].t[0], set, old);
-#endif
-            }
-        }
-    });
-    return img;
-}
-
-}  // namespace hdfs3crc
-
-namespace {
-
-int hip_fail(hipError_t e, const char *what) {
-    const int code = e == hipErrorOutOfMemory ? -ENOMEM
-                     : e == hipErrorInvalidValue ? -EINVAL
-                     : e == hipErrorNoDevice || e == hipErrorInvalidDevice ? -ENODEV
-                                                                           : -EIO;
-    return fail(code, "%s: %s", what, hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        hipError_t e_ = (expr);                        \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
-
-}  // namespace
-
 namespace {
 
 int check_args(hdfs3_crc_ctx *ctx, uint32_t bpc) {
@@ -119,31 +37,15 @@ int check_args(hdfs3_crc_ctx *ctx, uint32_t bpc) {
 }
 
 int grow_slot(Slot &s, size_t data_bytes, size_t crc_bytes) {
-    if (data_bytes > s.data_cap) {
-        if (s.h_data) (void)hipHostFree(s.h_data);
-        if (s.d_data) (void)hipFree(s.d_data);
-        s.h_data = s.d_data = nullptr;
-        s.data_cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_data), data_bytes, pinned_host_flags()));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_data), data_bytes));
-        s.data_cap = data_bytes;
-    }
-    if (crc_bytes > s.crc_cap) {
-        if (s.h_crc) (void)hipHostFree(s.h_crc);
-        if (s.d_crc) (void)hipFree(s.d_crc);
-        s.h_crc = s.d_crc = nullptr;
-        s.crc_cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_crc), crc_bytes, pinned_host_flags()));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s.d_crc), crc_bytes));
-        s.crc_cap = crc_bytes;
-    }
+    HIP_TRY(s.data.grow(data_bytes, pinned_host_flags()));
+    HIP_TRY(s.crc.grow(crc_bytes, pinned_host_flags()));
     return 0;
 }
 
 int finish_pending(Slot &s) {
     if (s.pending_out) {
         HIP_TRY(hipEventSynchronize(s.done));
-        std::memcpy(s.pending_out, s.h_crc, s.pending_bytes);
+        std::memcpy(s.pending_out, s.crc.h, s.pending_bytes);
         s.pending_out = nullptr;
         s.pending_bytes = 0;
     }
@@ -154,6 +56,17 @@ int launch(hdfs3_crc_ctx *ctx, const ChunkLaunch &a, bool verify) {
     HIP_TRY(launch_chunks(launch_env(ctx), a, verify));
     ++ctx->launches;
     return 0;
+}
+
+// the block checksums compute their chunk words in pieces of this many chunks
+constexpr uint64_t kMd5PieceChunks = 1ull << 20;  // 4 MiB of CRC words per piece
+
+// the compute launch over piece i of [d_data, d_data + len): its words go to d_words
+int launch_piece(hdfs3_crc_ctx *ctx, const void *d_data, size_t len, uint32_t bpc, uint64_t i, uint8_t *d_words) {
+    const uint64_t off = i * kMd5PieceChunks * bpc;
+    const uint64_t n = std::min<uint64_t>(kMd5PieceChunks * bpc, uint64_t(len) - off);
+    const uint8_t *piece = static_cast<const uint8_t *>(d_data) + off;
+    return launch(ctx, contiguous_launch(piece, n, bpc, nullptr, d_words, nullptr, 0, 0, false), false);
 }
 
 // true when [p, p+len) is page-locked host memory the DMA engine can read directly
@@ -167,6 +80,21 @@ bool is_pinned_host(const void *p) {
     return attr.type == hipMemoryTypeHost && attr.hostPointer != nullptr;
 }
 
+// The blocking verify calls' verdict: the ctx's result word is cleared before their launches ...
+int clear_verdict(hdfs3_crc_ctx *ctx) {
+    HIP_TRY(hipMemsetAsync(ctx->result.d, 0, sizeof(unsigned long long), ctx->stream));
+    return 0;
+}
+
+// ... and read back behind them: the stream is drained, *raw is the word as the kernels left it
+int read_verdict(hdfs3_crc_ctx *ctx, unsigned long long *raw) {
+    HIP_TRY(hipMemcpyAsync(ctx->result.h, ctx->result.d, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *raw = *ctx->result.h;
+    return 0;
+}
+
 // Host-buffer pipeline shared by compute and verify: segments of whole chunks
 // alternate between two pinned/device slots, so the CPU copy into pinned memory
 // of segment i+1 overlaps the DMA and kernel of segment i.
@@ -176,9 +104,8 @@ int host_pipeline_impl(hdfs3_crc_ctx *ctx, const void *data, size_t len, uint32_
     const bool verify = crc_in != nullptr;
     const size_t seg = (kSegmentBytes / bpc > 0 ? kSegmentBytes / bpc : 1) * size_t(bpc);
     const size_t seg_crc = (seg / bpc) * 4;
-    if (verify) {
-        HIP_TRY(hipMemsetAsync(ctx->d_result, 0, sizeof(unsigned long long), ctx->stream));
-    }
+    if (verify)
+        if (int rc = clear_verdict(ctx)) return rc;
     const uint8_t *src = static_cast<const uint8_t *>(data);
     const bool direct = is_pinned_host(data);  // skip the staging copy for pinned callers
     size_t off = 0;
@@ -190,25 +117,17 @@ int host_pipeline_impl(hdfs3_crc_ctx *ctx, const void *data, size_t len, uint32_
         if (s.done) HIP_TRY(hipEventSynchronize(s.done));
         if (int rc = finish_pending(s)) return rc;
         if (int rc = grow_slot(s, seg, seg_crc)) return rc;
-        if (!direct) CopyPool::get().copy(s.h_data, src + off, n);  // pageable: staged, split over the pool
-        HIP_TRY(hipMemcpyAsync(s.d_data, direct ? src + off : s.h_data, n, hipMemcpyHostToDevice, ctx->stream));
-        ChunkLaunch a{};
-        a.data = s.d_data;
-        a.len = n;
-        a.bpc = bpc;
-        a.chunk_base = chunk0;
-        a.check_short_tail = check_short_tail;
+        if (!direct) CopyPool::get().copy(s.data.h, src + off, n);  // pageable: staged, split over the pool
+        HIP_TRY(hipMemcpyAsync(s.data.d, direct ? src + off : s.data.h, n, hipMemcpyHostToDevice, ctx->stream));
         if (verify) {
-            std::memcpy(s.h_crc, static_cast<const uint8_t *>(crc_in) + 4 * chunk0, 4 * nc);
-            HIP_TRY(hipMemcpyAsync(s.d_crc, s.h_crc, 4 * nc, hipMemcpyHostToDevice, ctx->stream));
-            a.crc_be = s.d_crc;
-            a.result = ctx->d_result;
-        } else {
-            a.out_be = s.d_crc;
+            std::memcpy(s.crc.h, static_cast<const uint8_t *>(crc_in) + 4 * chunk0, 4 * nc);
+            HIP_TRY(hipMemcpyAsync(s.crc.d, s.crc.h, 4 * nc, hipMemcpyHostToDevice, ctx->stream));
         }
+        const ChunkLaunch a = contiguous_launch(s.data.d, n, bpc, verify ? s.crc.d : nullptr, verify ? nullptr : s.crc.d,
+                                                verify ? ctx->result.d : nullptr, chunk0, check_short_tail, false);
         if (int rc = launch(ctx, a, verify)) return rc;
         if (!verify) {
-            HIP_TRY(hipMemcpyAsync(s.h_crc, s.d_crc, 4 * nc, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(s.crc.h, s.crc.d, 4 * nc, hipMemcpyDeviceToHost, ctx->stream));
             s.pending_out = static_cast<uint8_t *>(crc_out) + 4 * chunk0;
             s.pending_bytes = 4 * nc;
         }
@@ -216,14 +135,15 @@ int host_pipeline_impl(hdfs3_crc_ctx *ctx, const void *data, size_t len, uint32_
         HIP_TRY(hipEventRecord(s.done, ctx->stream));
         off += n;
     }
+    unsigned long long raw = 0;
     if (verify) {
-        HIP_TRY(hipMemcpyAsync(ctx->h_result, ctx->d_result, sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, ctx->stream));
+        if (int rc = read_verdict(ctx, &raw)) return rc;
+    } else {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (Slot &s : ctx->slot)
         if (int rc = finish_pending(s)) return rc;
-    if (verify && first_bad) *first_bad = hdfs3_crc_decode_result(*ctx->h_result);
+    if (verify && first_bad) *first_bad = hdfs3_crc_decode_result(raw);
     return 0;
 }
 
@@ -272,12 +192,12 @@ int packets_async(hdfs3_crc_ctx *ctx, const uint8_t *d_arena, size_t arena_len, 
         dc.copied = st->copied;
         env.desc_copy = &dc;
     }
-    const hipError_t e = launch_packet_batch(env, d_arena, hp, n, bpc, verify, check_short_tail, d_result, st->h, st->d,
+    const hipError_t e = launch_packet_batch(env, d_arena, hp, n, bpc, verify, check_short_tail, d_result, st->seg.h, st->seg.d,
                                              arena_len, &bad, overlap, &staged);
     if (e == hipErrorInvalidValue) return fail(-EINVAL, "packet %zu lies outside the %zu-byte arena", bad, arena_len);
     HIP_TRY(e);
     ++ctx->launches;
-    // the launch copied its descriptors out of st->h asynchronously (the segmented kernel's array, the
+    // the launch copied its descriptors out of st->seg.h asynchronously (the segmented kernel's array, the
     // chunk-per-lane kernel's DevPackets): the slot is reused only after that copy ran (round 5:
     // unarmed, a fifth async batch could overwrite a queued copy's source). A launch whose arguments
     // carried everything (the pitch walk: the writer's and the wire-layout batches) records nothing:
@@ -292,20 +212,17 @@ int packets_async(hdfs3_crc_ctx *ctx, const uint8_t *d_arena, size_t arena_len, 
 int packets_common(hdfs3_crc_ctx *ctx, const uint8_t *d_arena, size_t arena_len,
                    const hdfs3_pkt_desc *pk, size_t n, uint32_t bpc, bool verify,
                    int check_short_tail, int64_t *bad_packet, int64_t *bad_chunk) {
-    if (verify) HIP_TRY(hipMemsetAsync(ctx->d_result, 0, sizeof(unsigned long long), ctx->stream));
-    if (int rc = packets_async(ctx, d_arena, arena_len, pk, n, bpc, verify, check_short_tail, ctx->d_result, false))
+    if (verify)
+        if (int rc = clear_verdict(ctx)) return rc;
+    if (int rc = packets_async(ctx, d_arena, arena_len, pk, n, bpc, verify, check_short_tail, ctx->result.d, false))
         return rc;
-    if (verify) {
-        HIP_TRY(hipMemcpyAsync(ctx->h_result, ctx->d_result, sizeof(unsigned long long),
-                               hipMemcpyDeviceToHost, ctx->stream));
+    if (!verify) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return 0;
     }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (verify) {
-        const unsigned long long r = *ctx->h_result;
-        const uint64_t key = r ? ~r : 0;
-        if (bad_packet) *bad_packet = r ? int64_t(key >> 32) : -1;
-        if (bad_chunk) *bad_chunk = r ? int64_t(key & 0xFFFFFFFFu) : -1;
-    }
+    unsigned long long raw = 0;
+    if (int rc = read_verdict(ctx, &raw)) return rc;
+    split_result_key(raw, bad_packet, bad_chunk);
     return 0;
 }
 
@@ -347,15 +264,7 @@ int stage_segments(hdfs3_crc_ctx *ctx, size_t n, hdfs3_crc_ctx::SegStage **out) 
     hdfs3_crc_ctx::SegStage &st = ctx->seg_ring[ctx->seg_next++ & 3u];
     if (st.armed) HIP_TRY(hipEventSynchronize(st.done));
     st.armed = false;
-    if (n > st.cap) {
-        if (st.h) (void)hipHostFree(st.h);
-        if (st.d) (void)hipFree(st.d);
-        st.h = st.d = nullptr;
-        st.cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st.h), n * sizeof(DevSegment), hipHostMallocDefault));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&st.d), n * sizeof(DevSegment)));
-        st.cap = n;
-    }
+    HIP_TRY(st.seg.grow(n * sizeof(DevSegment), hipHostMallocDefault));
     if (!st.done) HIP_TRY(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
     *out = &st;
     return 0;
@@ -372,25 +281,25 @@ int blocks_common(hdfs3_crc_ctx *ctx, const hdfs3_dev_block *blocks, size_t n, u
     hdfs3_crc_ctx::SegStage *st = nullptr;
     if (int rc = stage_segments(ctx, n, &st)) return rc;
     for (size_t i = 0; i < n; ++i)
-        st->h[i] = DevSegment{static_cast<const uint8_t *>(blocks[i].data), static_cast<uint8_t *>(blocks[i].crc_be),
+        st->seg.h[i] = DevSegment{static_cast<const uint8_t *>(blocks[i].data), static_cast<uint8_t *>(blocks[i].crc_be),
                               blocks[i].len, 0, uint64_t(i) << 32};
     // blocks of one 2-D tensor (constant data and word strides, equal whole-round blocks): the
     // wave kernel walks them directly (pitch mode); everything else: the segmented kernel
     const LaunchEnv env = launch_env(ctx);
     PitchStream s;
-    if (plan_strided_blocks(st->h, n, bpc, g_variant, &s)) {
+    if (plan_strided_blocks(st->seg.h, n, bpc, g_variant, &s)) {
         HIP_TRY(launch_packet_stream(
-            env, pitch_stream_launch(s, st->h[0].data, st->h[0].crc, bpc, check_short_tail, d_result), verify));
+            env, pitch_stream_launch(s, st->seg.h[0].data, st->seg.h[0].crc, bpc, check_short_tail, d_result), verify));
         ++ctx->launches;
-    } else if (segments_fast(st->h, n, bpc)) {
+    } else if (segments_fast(st->seg.h, n, bpc)) {
         uint64_t uniform = 0;
-        const uint64_t units = plan_segments(st->h, n, bpc, &uniform);
+        const uint64_t units = plan_segments(st->seg.h, n, bpc, &uniform);
         if (n <= kInlineSegments) {  // descriptors in the kernel arguments: no copy first
             HIP_TRY(launch_segments(env, nullptr, uint32_t(n), units, uniform, bpc, verify, check_short_tail, d_result,
-                                    st->h));
+                                    st->seg.h));
         } else {
-            HIP_TRY(hipMemcpyAsync(st->d, st->h, n * sizeof(DevSegment), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(launch_segments(env, st->d, uint32_t(n), units, uniform, bpc, verify, check_short_tail, d_result));
+            HIP_TRY(hipMemcpyAsync(st->seg.d, st->seg.h, n * sizeof(DevSegment), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(launch_segments(env, st->seg.d, uint32_t(n), units, uniform, bpc, verify, check_short_tail, d_result));
             // the pinned staging is read by the copy: reusable once it ran. The other paths read
             // it on the host only (the launch's arguments carry what the kernel needs), and an
             // event between launches costs a marker packet (~4 us of idle between barriered
@@ -402,15 +311,9 @@ int blocks_common(hdfs3_crc_ctx *ctx, const hdfs3_dev_block *blocks, size_t n, u
     } else {  // other chunk sizes or unaligned buffers: one launch per block, same keys
         for (size_t i = 0; i < n; ++i) {
             if (!blocks[i].len) continue;
-            ChunkLaunch a{};
-            a.data = st->h[i].data;
-            a.len = blocks[i].len;
-            a.bpc = bpc;
-            a.crc_be = st->h[i].crc;
-            a.out_be = st->h[i].crc;
-            a.result = d_result;
-            a.chunk_base = uint64_t(i) << 32;
-            a.check_short_tail = check_short_tail;
+            const DevSegment &b = st->seg.h[i];
+            const ChunkLaunch a =
+                contiguous_launch(b.data, b.len, bpc, b.crc, b.crc, d_result, b.key_base, check_short_tail, false);
             if (int rc = launch(ctx, a, verify)) return rc;
         }
     }
@@ -438,17 +341,11 @@ int hdfs3_crc32c_verify_blocks_dev(hdfs3_crc_ctx *ctx, const hdfs3_dev_block *bl
     if (n == 0) return 0;
     if (!blocks) return fail(-EINVAL, "null argument");
     DeviceGuard g(ctx->device);
-    HIP_TRY(hipMemsetAsync(ctx->d_result, 0, sizeof(unsigned long long), ctx->stream));
-    if (int rc = blocks_common(ctx, blocks, n, bpc, true, check_short_tail, ctx->d_result)) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_result, ctx->d_result, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const unsigned long long r = *ctx->h_result;
-    if (r) {
-        const uint64_t key = ~r;
-        if (bad_block) *bad_block = int64_t(key >> 32);
-        if (bad_chunk) *bad_chunk = int64_t(key & 0xFFFFFFFFu);
-    }
+    if (int rc = clear_verdict(ctx)) return rc;
+    if (int rc = blocks_common(ctx, blocks, n, bpc, true, check_short_tail, ctx->result.d)) return rc;
+    unsigned long long raw = 0;
+    if (int rc = read_verdict(ctx, &raw)) return rc;
+    split_result_key(raw, bad_block, bad_chunk);
     return 0;
 }
 
@@ -462,285 +359,13 @@ int hdfs3_crc32c_compute_blocks_dev(hdfs3_crc_ctx *ctx, const hdfs3_dev_block *b
 
 int hdfs3_crc_abi_version(void) { return HDFS3_CRC_ABI_VERSION; }
 
-const char *hdfs3_crc_last_error(void) { return g_err; }
-
 int hdfs3_device_count(int *count) {
     if (!count) return fail(-EINVAL, "null count");
     HIP_TRY(hipGetDeviceCount(count));
     return 0;
 }
 
-int hdfs3_crc_ctx_create(int device, hdfs3_crc_ctx **out) {
-    if (!out) return fail(-EINVAL, "null out");
-    *out = nullptr;
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(-ENODEV, "device %d not present (%d visible)", device, ndev);
-    hdfs3_crc_ctx *ctx = new (std::nothrow) hdfs3_crc_ctx();
-    if (!ctx) return fail(-ENOMEM, "ctx allocation");
-    ctx->device = device;
-    DeviceGuard g(device);
-    auto bail = [&](int rc) {
-        hdfs3_crc_ctx_destroy(ctx);
-        return rc;
-    };
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return bail(fail(-EIO, "hipGetDeviceProperties(%d) failed", device));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return bail(fail(-ENODEV, "device %d is %s; this build targets gfx950 (MI355X) only",
-                         device, prop.gcnArchName));
-    ctx->grid_cap = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(fail(-EIO, "hipStreamCreate failed"));
-    ctx->stream = ctx->own_stream;
-    if (hipMalloc(reinterpret_cast<void **>(&ctx->d_result), sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&ctx->h_result), sizeof(unsigned long long),
-                      hipHostMallocDefault) != hipSuccess)
-        return bail(fail(-ENOMEM, "device allocation for ctx failed"));
-    const HostImage *img = host_images();
-    for (int p = 0; p < 2; ++p) {
-        if (hipMalloc(reinterpret_cast<void **>(&ctx->d_tables_by[p]), sizeof(img[p].t)) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&ctx->d_fold_by[p]), kFoldUploadBytes) != hipSuccess)
-            return bail(fail(-ENOMEM, "device allocation for ctx failed"));
-        if (hipMemcpy(ctx->d_tables_by[p], img[p].t, sizeof(img[p].t), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(ctx->d_fold_by[p], img[p].fold, kFoldUploadBytes, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(-EIO, "table upload failed"));
-    }
-    ctx->d_tables = ctx->d_tables_by[0];
-    ctx->d_fold = ctx->d_fold_by[0];
-    ctx->poly = kPolyReflected;
-    *out = ctx;
-    return 0;
-}
-
-void hdfs3_crc_ctx_destroy(hdfs3_crc_ctx *ctx) {
-    if (!ctx) return;
-    DeviceGuard g(ctx->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (Slot &s : ctx->slot) {
-        if (s.h_data) (void)hipHostFree(s.h_data);
-        if (s.h_crc) (void)hipHostFree(s.h_crc);
-        if (s.d_data) (void)hipFree(s.d_data);
-        if (s.d_crc) (void)hipFree(s.d_crc);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    for (PacketArena &a : ctx->arena_cache) a.release();
-    ctx->arena_cache.clear();
-    for (auto &st : ctx->seg_ring) {
-        if (st.h) (void)hipHostFree(st.h);
-        if (st.d) (void)hipFree(st.d);
-        if (st.done) (void)hipEventDestroy(st.done);
-        if (st.copied) (void)hipEventDestroy(st.copied);
-    }
-    if (ctx->desc_stream) {
-        (void)hipStreamSynchronize(ctx->desc_stream);
-        (void)hipStreamDestroy(ctx->desc_stream);
-    }
-    ctx->words.release();
-    ctx->pieces.release();
-    ctx->compose.release();
-    for (int p = 0; p < 2; ++p) {
-        if (ctx->d_tables_by[p]) (void)hipFree(ctx->d_tables_by[p]);
-        if (ctx->d_fold_by[p]) (void)hipFree(ctx->d_fold_by[p]);
-    }
-    if (ctx->d_result) (void)hipFree(ctx->d_result);
-    if (ctx->h_result) (void)hipHostFree(ctx->h_result);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
-}
-
 }  // extern "C"
-
-namespace hdfs3crc {
-namespace {
-std::mutex g_ctx_pool_mu;
-std::vector<hdfs3_crc_ctx *> g_ctx_pool;
-constexpr size_t kCtxPoolMax = 32;
-constexpr size_t kArenaCacheKeep = 6;  // arenas any pooled ctx keeps (block_reader.cpp kArenaCacheMax)
-constexpr size_t kDeepCtxMax = 8;      // pooled contexts allowed to keep a read-ahead ring's worth
-// 1 GiB: the rings of a read-ahead stream up to depth 3 (whole 128 MiB blocks) plus the usual
-// shallow contexts; with 512 MiB, depth 2 / 3 read 9.1-10.7 / 5.1-7.0 GiB/s against 13.2-13.9 /
-// 11.1-14.1 (every open re-pinned rings the pool had shed; profiles/r03/reentry/r3e2e_caps_*)
-constexpr uint64_t kPoolPinnedDefault = uint64_t(1) << 30;
-
-// HDFS3_POOL_PINNED_MAX: bytes, or with a K/M/G suffix
-uint64_t pool_pinned_cap() {
-    static const uint64_t cap = [] {
-        const char *e = std::getenv("HDFS3_POOL_PINNED_MAX");
-        if (!e || !*e) return kPoolPinnedDefault;
-        char *end = nullptr;
-        const unsigned long long v = std::strtoull(e, &end, 10);
-        const int shift = *end == 'K' || *end == 'k' ? 10 : *end == 'M' || *end == 'm' ? 20
-                          : *end == 'G' || *end == 'g' ? 30 : 0;
-        // a whole number with at most one K/M/G suffix; anything else ("1.5G", "64MiB", "-1")
-        // is not silently read as a prefix of itself: the default stays and a warning says so
-        const char *rest = end + (shift ? 1 : 0);
-        if (end == e || *e == '-' || *rest != '\0' || (shift && v > (~0ull >> shift))) {
-            std::fprintf(stderr, "libhdfs3_crc: HDFS3_POOL_PINNED_MAX=\"%s\" is not a byte count "
-                                 "(digits with an optional K/M/G suffix); using the default %llu bytes\n",
-                         e, (unsigned long long)kPoolPinnedDefault);
-            return kPoolPinnedDefault;
-        }
-        return uint64_t(v) << shift;
-    }();
-    return cap;
-}
-
-struct Footprint {
-    uint64_t pinned = 0, device = 0;
-};
-
-// what a ctx holds beyond its tables: pinned host and device bytes of its staging slots, cached
-// arenas (with their piece scratch), descriptor stagings, word and piece scratch and result word
-Footprint footprint(hdfs3_crc_ctx *ctx) {
-    Footprint f;
-    for (const Slot &s : ctx->slot) {
-        f.pinned += s.data_cap + s.crc_cap;
-        f.device += s.data_cap + s.crc_cap;
-    }
-    {
-        std::lock_guard<std::mutex> lk(ctx->arena_mu);
-        for (const PacketArena &a : ctx->arena_cache) {
-            const uint64_t desc = a.desc_cap * sizeof(DevSegment) + (a.h_res ? sizeof(unsigned long long) : 0);
-            f.pinned += a.cap + desc;
-            // the arena's own piece scratch (bpc = R x 4096 batches) stays allocated while it is cached
-            f.device += a.cap + desc + a.pieces.cap[0] + a.pieces.cap[1];
-        }
-    }
-    for (const auto &st : ctx->seg_ring) {
-        f.pinned += st.cap * sizeof(DevSegment);
-        f.device += st.cap * sizeof(DevSegment);
-    }
-    f.pinned += sizeof(unsigned long long);
-    f.device += ctx->words.cap + ctx->pieces.cap[0] + ctx->pieces.cap[1] + sizeof(unsigned long long);
-    f.device += ctx->compose.words_cap + ctx->compose.partials_cap;
-    for (int p = 0; p < 2; ++p) f.device += sizeof(host_images()[p].t) + kFoldUploadBytes;
-    return f;
-}
-
-// give back what a pooled ctx can rebuild on demand: cached arenas beyond `keep`, then the
-// staging slots of the host API
-void shed(hdfs3_crc_ctx *ctx, size_t keep_arenas, bool slots) {
-    DeviceGuard g(ctx->device);
-    {
-        std::lock_guard<std::mutex> alk(ctx->arena_mu);
-        while (ctx->arena_cache.size() > keep_arenas) {
-            ctx->arena_cache.back().release();
-            ctx->arena_cache.pop_back();
-        }
-    }
-    if (!slots) return;
-    for (Slot &s : ctx->slot) {
-        if (s.h_data) (void)hipHostFree(s.h_data);
-        if (s.h_crc) (void)hipHostFree(s.h_crc);
-        if (s.d_data) (void)hipFree(s.d_data);
-        if (s.d_crc) (void)hipFree(s.d_crc);
-        s.h_data = s.h_crc = s.d_data = s.d_crc = nullptr;
-        s.data_cap = s.crc_cap = 0;
-    }
-}
-}  // namespace
-
-uint64_t pool_pinned_cap_bytes() { return pool_pinned_cap(); }
-
-std::mutex &pool_admission_mu() {
-    static std::mutex mu;
-    return mu;
-}
-
-void ctx_footprint(hdfs3_crc_ctx *ctx, uint64_t *pinned, uint64_t *device) {
-    const Footprint f = footprint(ctx);
-    if (pinned) *pinned = f.pinned;
-    if (device) *device = f.device;
-}
-
-uint64_t ctx_pool_pinned_bytes() {
-    std::lock_guard<std::mutex> lk(g_ctx_pool_mu);
-    uint64_t n = 0;
-    for (hdfs3_crc_ctx *c : g_ctx_pool) n += footprint(c).pinned;
-    return n;
-}
-
-int ctx_acquire(int device, hdfs3_crc_ctx **out, bool deep) {
-    if (!out) return fail(-EINVAL, "null out");
-    {
-        std::lock_guard<std::mutex> lk(g_ctx_pool_mu);
-        // deep: the pooled ctx with the most cached arenas (a read-ahead reader's ring);
-        // otherwise the one with the fewest, which keeps the deep ones for read-ahead
-        long best = -1;
-        for (size_t i = 0; i < g_ctx_pool.size(); ++i) {
-            if (g_ctx_pool[i]->device != device) continue;
-            if (best < 0 || (deep ? g_ctx_pool[i]->arena_cache.size() > g_ctx_pool[size_t(best)]->arena_cache.size()
-                                  : g_ctx_pool[i]->arena_cache.size() < g_ctx_pool[size_t(best)]->arena_cache.size()))
-                best = long(i);
-        }
-        if (best >= 0) {
-            hdfs3_crc_ctx *ctx = g_ctx_pool[size_t(best)];
-            g_ctx_pool.erase(g_ctx_pool.begin() + best);
-            ctx->stream = ctx->own_stream;
-            ctx->checksum_type = HDFS3_CHECKSUM_TYPE_CRC32C;
-            ctx->d_tables = ctx->d_tables_by[0];
-            ctx->d_fold = ctx->d_fold_by[0];
-            ctx->poly = kPolyReflected;
-            *out = ctx;
-            return 0;
-        }
-    }
-    return hdfs3_crc_ctx_create(device, out);
-}
-
-void ctx_release(hdfs3_crc_ctx *ctx) {
-    if (!ctx) return;
-    bool ok;
-    {
-        DeviceGuard g(ctx->device);
-        ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
-    }
-    for (Slot &s : ctx->slot) s.pending_out = nullptr;
-    if (ok) {
-        // one admission at a time across both pools (pool_admission_mu): the short-circuit readers'
-        // pool counts against the same cap, and its bytes cannot grow while this decision is made
-        std::lock_guard<std::mutex> adm(pool_admission_mu());
-        const uint64_t local = local_pool_stats().pinned;
-        std::lock_guard<std::mutex> lk(g_ctx_pool_mu);
-        if (g_ctx_pool.size() < kCtxPoolMax) {
-            // a read-ahead reader's deep ring leaves up to a block's worth of pinned arenas in
-            // its ctx (block_reader.cpp); at most kDeepCtxMax pooled contexts keep that much,
-            // the others go back to the usual few arenas
-            size_t deep = 0;
-            for (hdfs3_crc_ctx *c : g_ctx_pool) deep += c->arena_cache.size() > kArenaCacheKeep;
-            if (deep >= kDeepCtxMax && ctx->arena_cache.size() > kArenaCacheKeep) shed(ctx, kArenaCacheKeep, false);
-            // and the pool as a whole retains at most pool_pinned_cap() pinned bytes. The ctx released
-            // last is the one most likely to be taken again soon (a read-ahead stream releases the
-            // ring of the block it finished and at once acquires a deep ctx for the next block ahead),
-            // so the pooled contexts give back their arenas first, least recently released first
-            // (the pool's front); then this ctx sheds arenas and staging, and is destroyed if it still
-            // does not fit. Shedding this ctx first made every read-ahead block re-pin its ring once
-            // older pooled rings filled the cap: 1 GiB with read-ahead 2 / 7 at 6.6 / 2.3 GiB/s
-            // against 11.8 / 10.6 uncapped (profiles/r03/reentry/r3e2eab_*).
-            const uint64_t cap = pool_pinned_cap() > local ? pool_pinned_cap() - local : 0;
-            const uint64_t mine = footprint(ctx).pinned;
-            uint64_t others = 0;
-            for (hdfs3_crc_ctx *c : g_ctx_pool) others += footprint(c).pinned;
-            for (const bool slots : {false, true})  // their arenas first, then their staging slots
-                for (size_t i = 0; i < g_ctx_pool.size() && others + mine > cap; ++i) {
-                    const uint64_t before = footprint(g_ctx_pool[i]).pinned;
-                    shed(g_ctx_pool[i], 0, slots);
-                    others -= before - footprint(g_ctx_pool[i]).pinned;
-                }
-            if (others + footprint(ctx).pinned > cap) shed(ctx, 0, false);
-            if (others + footprint(ctx).pinned > cap) shed(ctx, 0, true);
-            if (others + footprint(ctx).pinned <= cap) {
-                g_ctx_pool.push_back(ctx);
-                return;
-            }
-        }
-    }
-    hdfs3_crc_ctx_destroy(ctx);
-}
-
-}  // namespace hdfs3crc
 
 namespace hdfs3crc {
 int gather_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len, const CopyRange *r,
@@ -792,76 +417,6 @@ int deliver_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_s
 
 extern "C" {
 
-int hdfs3_crc_ctx_acquire(int device, hdfs3_crc_ctx **out) { return hdfs3crc::ctx_acquire(device, out); }
-void hdfs3_crc_ctx_release(hdfs3_crc_ctx *ctx) { hdfs3crc::ctx_release(ctx); }
-
-int hdfs3_crc_pool_stats_get(hdfs3_crc_pool_stats *out) {
-    if (!out) return fail(-EINVAL, "null out");
-    hdfs3_crc_pool_stats st{};
-    // The short-circuit readers' pooled contexts and windows are part of the same budget. The two pools
-    // are read one after the other: without the admission lock an entry taken out of the first and a ctx
-    // admitted into the second in between were both counted, a sum above the cap that never existed. With
-    // it only removals can fall between the two reads, so the sum is at most what was retained.
-    std::lock_guard<std::mutex> adm(hdfs3crc::pool_admission_mu());
-    const hdfs3crc::LocalPoolStats lp = hdfs3crc::local_pool_stats();
-    std::lock_guard<std::mutex> lk(hdfs3crc::g_ctx_pool_mu);
-    for (hdfs3_crc_ctx *c : hdfs3crc::g_ctx_pool) {
-        const hdfs3crc::Footprint f = hdfs3crc::footprint(c);
-        st.pinned_bytes += f.pinned;
-        st.device_bytes += f.device;
-    }
-    st.pinned_bytes += lp.pinned;
-    st.device_bytes += lp.device;
-    st.pooled_contexts = hdfs3crc::g_ctx_pool.size() + lp.entries;
-    st.pinned_cap_bytes = hdfs3crc::pool_pinned_cap();
-    *out = st;
-    return 0;
-}
-
-int hdfs3_crc_pool_trim(void) {
-    const int local = hdfs3crc::local_pool_trim();
-    std::vector<hdfs3_crc_ctx *> idle;
-    {
-        std::lock_guard<std::mutex> lk(hdfs3crc::g_ctx_pool_mu);
-        idle.swap(hdfs3crc::g_ctx_pool);
-    }
-    for (hdfs3_crc_ctx *c : idle) hdfs3_crc_ctx_destroy(c);
-    return int(idle.size()) + local;
-}
-
-int hdfs3_crc_ctx_set_stream(hdfs3_crc_ctx *ctx, void *hip_stream) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
-    return 0;
-}
-
-void *hdfs3_crc_ctx_get_stream(hdfs3_crc_ctx *ctx) { return ctx ? ctx->stream : nullptr; }
-
-int hdfs3_crc_ctx_set_checksum_type(hdfs3_crc_ctx *ctx, int type) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    if (type != HDFS3_CHECKSUM_TYPE_CRC32C && type != HDFS3_CHECKSUM_TYPE_CRC32)
-        return fail(-EINVAL, "checksum type %d has no CRC polynomial", type);
-    const int i = type == HDFS3_CHECKSUM_TYPE_CRC32C ? 0 : 1;
-    ctx->d_tables = ctx->d_tables_by[i];
-    ctx->d_fold = ctx->d_fold_by[i];
-    ctx->poly = i == 0 ? kPolyReflected : kPolyCrc32;
-    ctx->checksum_type = type;
-    return 0;
-}
-
-int hdfs3_crc_ctx_get_checksum_type(hdfs3_crc_ctx *ctx) { return ctx ? ctx->checksum_type : -EINVAL; }
-
-int hdfs3_crc_ctx_synchronize(hdfs3_crc_ctx *ctx) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-uint64_t hdfs3_crc_ctx_kernel_launches(hdfs3_crc_ctx *ctx) { return ctx ? ctx->launches.load() : 0; }
-
 int64_t hdfs3_crc_decode_result(uint64_t r) { return r ? int64_t(~r) : -1; }
 
 int hdfs3_crc32c_compute(hdfs3_crc_ctx *ctx, const void *data, size_t len, uint32_t bpc,
@@ -889,12 +444,7 @@ int hdfs3_crc32c_compute_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len,
     if (len == 0) return 0;
     if (!d_data || !d_crc_be_out) return fail(-EINVAL, "null buffer");
     DeviceGuard g(ctx->device);
-    ChunkLaunch a{};
-    a.data = static_cast<const uint8_t *>(d_data);
-    a.len = len;
-    a.bpc = bpc;
-    a.out_be = static_cast<uint8_t *>(d_crc_be_out);
-    return launch(ctx, a, false);
+    return launch(ctx, contiguous_launch(d_data, len, bpc, nullptr, d_crc_be_out, nullptr, 0, 0, false), false);
 }
 
 int hdfs3_crc32c_compute_dev_async_ex(hdfs3_crc_ctx *ctx, const void *d_data, size_t len, uint32_t bpc,
@@ -904,13 +454,8 @@ int hdfs3_crc32c_compute_dev_async_ex(hdfs3_crc_ctx *ctx, const void *d_data, si
     if (len == 0) return 0;
     if (!d_data || !d_crc_be_out) return fail(-EINVAL, "null buffer");
     DeviceGuard g(ctx->device);
-    ChunkLaunch a{};
-    a.data = static_cast<const uint8_t *>(d_data);
-    a.len = len;
-    a.bpc = bpc;
-    a.out_be = static_cast<uint8_t *>(d_crc_be_out);
-    a.overlap_previous = (flags & HDFS3_LAUNCH_OVERLAP_PREVIOUS) != 0;
-    return launch(ctx, a, false);
+    const bool overlap = (flags & HDFS3_LAUNCH_OVERLAP_PREVIOUS) != 0;
+    return launch(ctx, contiguous_launch(d_data, len, bpc, nullptr, d_crc_be_out, nullptr, 0, 0, overlap), false);
 }
 
 int hdfs3_crc32c_verify_dev_async(hdfs3_crc_ctx *ctx, const void *d_data, size_t len,
@@ -927,15 +472,11 @@ int hdfs3_crc32c_verify_dev_async_ex(hdfs3_crc_ctx *ctx, const void *d_data, siz
     if (len == 0) return 0;
     if (!d_data || !d_crc_be || !d_result) return fail(-EINVAL, "null buffer");
     DeviceGuard g(ctx->device);
-    ChunkLaunch a{};
-    a.data = static_cast<const uint8_t *>(d_data);
-    a.len = len;
-    a.bpc = bpc;
-    a.crc_be = static_cast<const uint8_t *>(d_crc_be);
-    a.result = reinterpret_cast<unsigned long long *>(d_result);
-    a.check_short_tail = check_short_tail;
-    a.overlap_previous = (flags & HDFS3_LAUNCH_OVERLAP_PREVIOUS) != 0;
-    return launch(ctx, a, true);
+    const bool overlap = (flags & HDFS3_LAUNCH_OVERLAP_PREVIOUS) != 0;
+    return launch(ctx,
+                  contiguous_launch(d_data, len, bpc, d_crc_be, nullptr, reinterpret_cast<unsigned long long *>(d_result), 0,
+                                    check_short_tail, overlap),
+                  true);
 }
 
 int hdfs3_crc32c_verify_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len, uint32_t bpc,
@@ -944,14 +485,13 @@ int hdfs3_crc32c_verify_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len, 
     if (first_bad_chunk) *first_bad_chunk = -1;
     if (len == 0) return 0;
     DeviceGuard g(ctx->device);
-    HIP_TRY(hipMemsetAsync(ctx->d_result, 0, sizeof(unsigned long long), ctx->stream));
+    if (int rc = clear_verdict(ctx)) return rc;
     if (int rc = hdfs3_crc32c_verify_dev_async(ctx, d_data, len, bpc, d_crc_be, check_short_tail,
-                                               reinterpret_cast<uint64_t *>(ctx->d_result)))
+                                               reinterpret_cast<uint64_t *>(ctx->result.d)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_result, ctx->d_result, sizeof(unsigned long long),
-                           hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (first_bad_chunk) *first_bad_chunk = hdfs3_crc_decode_result(*ctx->h_result);
+    unsigned long long raw = 0;
+    if (int rc = read_verdict(ctx, &raw)) return rc;
+    if (first_bad_chunk) *first_bad_chunk = hdfs3_crc_decode_result(raw);
     return 0;
 }
 
@@ -968,9 +508,9 @@ int hdfs3_crc32c_verify_packets(hdfs3_crc_ctx *ctx, const void *arena, size_t ar
     if (s.done) HIP_TRY(hipEventSynchronize(s.done));
     if (int rc = finish_pending(s)) return rc;
     if (int rc = grow_slot(s, arena_len, 4)) return rc;
-    CopyPool::get().copy(s.h_data, arena, arena_len);  // split over the pool from 2 MiB up
-    HIP_TRY(hipMemcpyAsync(s.d_data, s.h_data, arena_len, hipMemcpyHostToDevice, ctx->stream));
-    return packets_common(ctx, s.d_data, arena_len, pk, n, bpc, true, check_short_tail, bad_packet,
+    CopyPool::get().copy(s.data.h, arena, arena_len);  // split over the pool from 2 MiB up
+    HIP_TRY(hipMemcpyAsync(s.data.d, s.data.h, arena_len, hipMemcpyHostToDevice, ctx->stream));
+    return packets_common(ctx, s.data.d, arena_len, pk, n, bpc, true, check_short_tail, bad_packet,
                           bad_chunk);
 }
 
@@ -1114,10 +654,6 @@ uint32_t hdfs3_crc32c_update_host(uint32_t state, const void *p, size_t len) {
 // Block checksum (include/hdfs3_crc.h): the CRC words come from the compute kernel in
 // pieces of up to kMd5PieceChunks chunks, alternating between the two slots, so the host
 // digests piece i while the GPU computes and copies out piece i+1.
-namespace {
-constexpr uint64_t kMd5PieceChunks = 1ull << 20;  // 4 MiB of CRC words per piece
-}
-
 int hdfs3_block_checksum_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len, uint32_t bpc,
                              uint8_t *md5_out, uint64_t *crc_per_block) {
     if (int rc = check_args(ctx, bpc)) return rc;
@@ -1136,15 +672,9 @@ int hdfs3_block_checksum_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len,
         }
         auto issue = [&](uint64_t i) -> int {
             Slot &s = ctx->slot[i & 1];
-            const uint64_t c0 = i * per, cn = std::min(per, n - c0);
-            const uint64_t off = c0 * bpc;
-            ChunkLaunch a{};
-            a.data = static_cast<const uint8_t *>(d_data) + off;
-            a.len = std::min<uint64_t>(cn * bpc, uint64_t(len) - off);
-            a.bpc = bpc;
-            a.out_be = s.d_crc;
-            if (int rc = launch(ctx, a, false)) return rc;
-            HIP_TRY(hipMemcpyAsync(s.h_crc, s.d_crc, size_t(cn) * 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (int rc = launch_piece(ctx, d_data, len, bpc, i, s.crc.d)) return rc;
+            HIP_TRY(hipMemcpyAsync(s.crc.h, s.crc.d, size_t(std::min(per, n - i * per)) * 4, hipMemcpyDeviceToHost,
+                                   ctx->stream));
             HIP_TRY(hipEventRecord(s.done, ctx->stream));
             return 0;
         };
@@ -1154,7 +684,7 @@ int hdfs3_block_checksum_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t len,
                 if (int rc = issue(i + 1)) return rc;
             Slot &s = ctx->slot[i & 1];
             HIP_TRY(hipEventSynchronize(s.done));
-            md5.update(s.h_crc, size_t(std::min(per, n - i * per)) * 4);
+            md5.update(s.crc.h, size_t(std::min(per, n - i * per)) * 4);
         }
     }
     md5.finish(md5_out);
@@ -1266,122 +796,16 @@ int hdfs3_block_composite_crc_dev(hdfs3_crc_ctx *ctx, const void *d_data, size_t
     ComposeScratch &cs = ctx->compose;
     HIP_TRY(grow_compose_buffer(&cs.words, &cs.words_cap, n * 4, ctx->stream));
     // the chunk words into the scratch, one compute launch per 4 Mi chunks as hdfs3_block_checksum_dev
-    for (uint64_t c0 = 0; c0 < n; c0 += kMd5PieceChunks) {
-        const uint64_t off = c0 * bpc;
-        ChunkLaunch a{};
-        a.data = static_cast<const uint8_t *>(d_data) + off;
-        a.len = std::min<uint64_t>(kMd5PieceChunks * bpc, uint64_t(len) - off);
-        a.bpc = bpc;
-        a.out_be = cs.words + 4 * c0;
-        if (int rc = launch(ctx, a, false)) return rc;
-    }
+    for (uint64_t i = 0; i * kMd5PieceChunks < n; ++i)
+        if (int rc = launch_piece(ctx, d_data, len, bpc, i, cs.words + 4 * i * kMd5PieceChunks)) return rc;
     // the result word shares the verify calls' slot: a ctx serves one call at a time
-    uint32_t *d_out = reinterpret_cast<uint32_t *>(ctx->d_result);
+    uint32_t *d_out = reinterpret_cast<uint32_t *>(ctx->result.d);
     const uint32_t last_len = uint32_t(uint64_t(len) - (n - 1) * bpc);
     if (int rc = compose_words(ctx, cs.words, n, bpc, last_len, d_out)) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->h_result, d_out, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->result.h, d_out, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *crc_out = *reinterpret_cast<const uint32_t *>(ctx->h_result);
-    return 0;
-}
-
-int hdfs3_dev_malloc(void **d_ptr, size_t bytes) {
-    if (!d_ptr) return fail(-EINVAL, "null out");
-    HIP_TRY(hipMalloc(d_ptr, bytes));
-    return 0;
-}
-
-int hdfs3_dev_free(void *d_ptr) {
-    HIP_TRY(hipFree(d_ptr));
-    return 0;
-}
-
-int hdfs3_host_malloc_pinned(void **h_ptr, size_t bytes) {
-    if (!h_ptr) return fail(-EINVAL, "null out");
-    HIP_TRY(hipHostMalloc(h_ptr, bytes, hipHostMallocDefault));
-    return 0;
-}
-
-int hdfs3_host_free_pinned(void *h_ptr) {
-    HIP_TRY(hipHostFree(h_ptr));
-    return 0;
-}
-
-int hdfs3_memcpy_h2d(hdfs3_crc_ctx *ctx, void *d_dst, const void *h_src, size_t bytes) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int hdfs3_memcpy_d2h(hdfs3_crc_ctx *ctx, void *h_dst, const void *d_src, size_t bytes) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int hdfs3_memset_dev(hdfs3_crc_ctx *ctx, void *d_dst, int value, size_t bytes) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(hipMemsetAsync(d_dst, value, bytes, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *crc_out = *reinterpret_cast<const uint32_t *>(ctx->result.h);
     return 0;
 }
 
 }  // extern "C"
-
-// ---- measurement hooks: libhdfs3_crc_lab.so only (HDFS3_LAB=1; bench.py's read ceiling,
-// tools/, the A/B tests). Not part of hdfs3_crc.h and not exported by libhdfs3_crc.so. ----
-#if HDFS3_LAB
-extern "C" {
-
-// Coalesced read-only stream over [d, d+len): the achievable HBM read ceiling.
-int hdfs3x_stream_read_ex(hdfs3_crc_ctx *ctx, const void *d, size_t len, int grid, void *d_sink, uint32_t flags);
-int hdfs3x_stream_read(hdfs3_crc_ctx *ctx, const void *d, size_t len, int grid, void *d_sink) {
-    return hdfs3x_stream_read_ex(ctx, d, len, grid, d_sink, 0);
-}
-
-// flags: HDFS3_LAUNCH_OVERLAP_PREVIOUS, for the same-shape ceiling of overlapped verifies
-int hdfs3x_stream_read_ex(hdfs3_crc_ctx *ctx, const void *d, size_t len, int grid, void *d_sink, uint32_t flags) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(launch_stream_read(static_cast<const uint8_t *>(d), len, static_cast<uint32_t *>(d_sink),
-                               grid != 0 ? grid : ctx->grid_cap * 8, ctx->stream,
-                               (flags & HDFS3_LAUNCH_OVERLAP_PREVIOUS) != 0));
-    return 0;
-}
-
-// The CRC kernel's chunk-per-lane access pattern without the table arithmetic.
-int hdfs3x_lane_read(hdfs3_crc_ctx *ctx, const void *d, size_t len, uint32_t bpc, void *d_sink) {
-    if (!ctx) return fail(-EINVAL, "null ctx");
-    DeviceGuard g(ctx->device);
-    HIP_TRY(launch_lane_read(static_cast<const uint8_t *>(d), len, bpc, static_cast<uint32_t *>(d_sink),
-                             ctx->grid_cap, ctx->stream));
-    return 0;
-}
-
-int hdfs3x_grid_cap(hdfs3_crc_ctx *ctx) { return ctx ? ctx->grid_cap : 0; }
-
-// Process-wide kernel-variant knob for in-process A/B measurements (tools/ab.py).
-void hdfs3x_set_variant(int v) { set_variant(v); }
-
-// Clock stamps of variant 125 and the stream-read kernel (tools/clock_ramp.py): installs a device
-// buffer of cap x 4 u64 ({s_memtime, s_memrealtime} at workgroup 0's start and end, one slot per
-// launch); returns the number of stamps written into the previous buffer, or a negative errno.
-int hdfs3x_clock_stamps(void *d_buf, unsigned int cap) {
-    unsigned int n = 0;
-    HIP_TRY(lab_clock_buffer(static_cast<unsigned long long *>(d_buf), cap, &n));
-    return int(n);
-}
-
-int hdfs3x_wave_stamps(void *d_buf, unsigned int cap) {
-    unsigned int n = 0;
-    HIP_TRY(lab_wave_buffer(static_cast<unsigned long long *>(d_buf), cap, &n));
-    return int(n);
-}
-
-}  // extern "C"
-#endif  // HDFS3_LAB

@@ -62,6 +62,15 @@ struct DevSegment {
     uint64_t key_base;
 };
 
+// A verify result word whose key has two halves (key_base above: index << 32 | chunk; the word holds ~key,
+// 0 while nothing was bad): *hi / *lo (either may be null) receive the halves, -1 / -1 for 0.
+// hdfs3_crc_decode_result is the one-part form for chunk keys.
+inline void split_result_key(unsigned long long raw, int64_t *hi, int64_t *lo) {
+    const uint64_t key = ~uint64_t(raw);
+    if (hi) *hi = raw ? int64_t(key >> 32) : -1;
+    if (lo) *lo = raw ? int64_t(key & 0xFFFFFFFFu) : -1;
+}
+
 // Units of a segment of len bytes at bpc <= 4096: its whole chunks cut into 4 KiB units, the
 // last one partial when the whole chunks end inside a round (PacketGeom); a short last chunk is
 // the kernel's one-lane tail

@@ -34,8 +34,7 @@ namespace {
 struct Worker {
     int device = 0;
     hdfs3_crc_ctx *ctx = nullptr;
-    unsigned long long *d_res = nullptr, *h_res = nullptr;
-    size_t res_cap = 0;
+    hdfs3crc::Mirror<unsigned long long> res;
 
     std::thread th;
     std::mutex mu;
@@ -79,15 +78,8 @@ struct Worker {
     }
     // per-block result words for n blocks (called on the worker thread)
     int reserve(size_t n) {
-        if (n <= res_cap) return 0;
-        if (d_res) (void)hipFree(d_res);
-        if (h_res) (void)hipHostFree(h_res);
-        d_res = h_res = nullptr;
-        res_cap = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&d_res), n * 8) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void **>(&h_res), n * 8, hdfs3crc::pinned_host_flags()) != hipSuccess)
+        if (res.grow(n * 8, hdfs3crc::pinned_host_flags()) != hipSuccess)
             return fail(-ENOMEM, "device %d: result array for %zu blocks", device, n);
-        res_cap = n;
         return 0;
     }
 };
@@ -197,8 +189,7 @@ void hdfs3_multi_destroy(hdfs3_multi *m) {
         if (wk->ctx) {
             hdfs3crc::DeviceGuard guard(wk->device);  // the caller's current device is left as it was
             hdfs3_crc_ctx_destroy(wk->ctx);
-            if (wk->d_res) (void)hipFree(wk->d_res);
-            if (wk->h_res) (void)hipHostFree(wk->h_res);
+            wk->res.release();
         }
         delete wk;
     }
@@ -215,7 +206,7 @@ int hdfs3_crc32c_verify_blocks_multi(hdfs3_multi *m, const hdfs3_dev_block *bloc
     return fan_out(m, n, [&](Worker &wk, const std::vector<size_t> &idx) -> int {
         if (int rc = wk.reserve(idx.size())) return rc;
         hipStream_t s = static_cast<hipStream_t>(hdfs3_crc_ctx_get_stream(wk.ctx));
-        if (hipMemsetAsync(wk.d_res, 0, idx.size() * 8, s) != hipSuccess)
+        if (hipMemsetAsync(wk.res.d, 0, idx.size() * 8, s) != hipSuccess)
             return fail(-EIO, "device %d: result memset failed", wk.device);
         bool prev_verify = false;  // the first launch stays barriered behind the memset
         for (size_t i = 0; i < idx.size(); ++i) {
@@ -224,15 +215,15 @@ int hdfs3_crc32c_verify_blocks_multi(hdfs3_multi *m, const hdfs3_dev_block *bloc
             // every block and word array was resident before the first launch and each verify
             // only reads them: later launches may overlap their predecessor (hdfs3_crc.h)
             if (int rc = hdfs3_crc32c_verify_dev_async_ex(wk.ctx, b.data, b.len, bpc, b.crc_be, check_short_tail,
-                                                          reinterpret_cast<uint64_t *>(wk.d_res + i),
+                                                          reinterpret_cast<uint64_t *>(wk.res.d + i),
                                                           prev_verify ? HDFS3_LAUNCH_OVERLAP_PREVIOUS : 0u))
                 return rc;
             prev_verify = true;
         }
-        if (hipMemcpyAsync(wk.h_res, wk.d_res, idx.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        if (hipMemcpyAsync(wk.res.h, wk.res.d, idx.size() * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess)
             return fail(-EIO, "device %d: verify failed", wk.device);
-        for (size_t i = 0; i < idx.size(); ++i) first_bad[idx[i]] = hdfs3_crc_decode_result(wk.h_res[i]);
+        for (size_t i = 0; i < idx.size(); ++i) first_bad[idx[i]] = hdfs3_crc_decode_result(wk.res.h[i]);
         return 0;
     });
 }

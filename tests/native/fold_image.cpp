@@ -65,7 +65,7 @@ int main() {
         build_slice_tables(t, poly);
         std::vector<uint32_t> fold(kFoldImageWords);
         build_fold_matrices(t[0], fold.data());
-        for (int set = 0; set < 4; ++set) {  // as hdfs3_crc.cpp host_images builds them
+        for (int set = 0; set < 4; ++set) {  // as ctx.cpp host_images builds them
             uint32_t *nib = fold.data() + kFoldAffineOff + set * kFoldNibbleWords;
             build_fold_nibbles_pre(t[0], fold.data(), set, nib);
             build_fold_affine(t[0], set, nib);

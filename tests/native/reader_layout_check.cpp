@@ -147,6 +147,24 @@ void result_mapping() {
     CHECK(w.bad_packet(~((5ull << 32) | 3)) == 5, "wire mapping");
 }
 
+// split_result_key (launch_plan.h): the word holds ~key, and 0 means nothing bad
+void result_key_cases() {
+    int64_t hi = 7, lo = 7;
+    split_result_key(0, &hi, &lo);
+    CHECK(hi == -1 && lo == -1, "raw 0: %lld / %lld", (long long)hi, (long long)lo);
+    split_result_key(~0ull, &hi, &lo);  // key 0: the first chunk of the first packet
+    CHECK(hi == 0 && lo == 0, "key 0: %lld / %lld", (long long)hi, (long long)lo);
+    split_result_key(~((5ull << 32) | 3), &hi, &lo);
+    CHECK(hi == 5 && lo == 3, "both halves: %lld / %lld", (long long)hi, (long long)lo);
+    // the largest key a non-zero word can hold (~1); the key of all ones would read as raw 0
+    split_result_key(1, &hi, &lo);
+    CHECK(hi == 0xFFFFFFFFll && lo == 0xFFFFFFFEll, "largest key: %lld / %lld", (long long)hi, (long long)lo);
+    hi = lo = 7;
+    split_result_key(~(9ull << 32), &hi, nullptr);
+    split_result_key(~4ull, nullptr, &lo);
+    CHECK(hi == 9 && lo == 4, "one half at a time: %lld / %lld", (long long)hi, (long long)lo);
+}
+
 void cursor_cases() {
     BatchLayout l;
     l.open(512, 512, 4, 8, true);
@@ -183,6 +201,7 @@ int main() {
     dense_cases();
     wire_cases();
     result_mapping();
+    result_key_cases();
     cursor_cases();
     if (g_failed) {
         std::printf("%d checks failed\n", g_failed);

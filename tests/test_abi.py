@@ -147,3 +147,48 @@ def test_pool_pinned_cap_parser(value, want_mib, warns):
     assert out.returncode == 0, out.stderr
     assert int(out.stdout.strip().splitlines()[-1]) == want_mib << 20
     assert ("HDFS3_POOL_PINNED_MAX" in out.stderr) == warns, out.stderr
+
+
+@pytest.mark.gpu
+def test_pool_stats_count_one_staging_slot():
+    """The bytes hdfs3_crc_pool_stats_get reports for a pooled ctx, pinned to the byte: a host verify of
+    1 MiB at bpc 512 makes the ctx allocate one staging slot, kSegmentBytes (16 MiB) of data plus 4 bytes
+    per 512-byte chunk of it (128 KiB), pinned and on the device alike; nothing else is added."""
+    from libhdfs3_amd import _native
+    from util import oracle_compute, ptr, splitmix_bytes
+
+    lib = _native.lib()
+    lib.hdfs3_crc_pool_trim()
+
+    def stats():
+        st = _native.PoolStats()
+        assert lib.hdfs3_crc_pool_stats_get(ctypes.byref(st)) == 0
+        return st
+
+    ctx = ctypes.c_void_p()
+    assert lib.hdfs3_crc_ctx_acquire(0, ctypes.byref(ctx)) == 0, lib.hdfs3_crc_last_error()
+    first = ctx.value
+    lib.hdfs3_crc_ctx_release(ctx)
+    a = stats()
+    assert a.pooled_contexts == 1
+
+    assert lib.hdfs3_crc_ctx_acquire(0, ctypes.byref(ctx)) == 0, lib.hdfs3_crc_last_error()
+    assert ctx.value == first  # the pool hands the same ctx back
+    data = splitmix_bytes(1 << 20, 7)
+    words = oracle_compute(data, 512)
+    bad = ctypes.c_int64(0)
+    assert lib.hdfs3_crc32c_verify(ctx, ptr(data), data.nbytes, 512, ptr(words), 0, ctypes.byref(bad)) == 0
+    assert bad.value == -1
+    lib.hdfs3_crc_ctx_release(ctx)
+    b = stats()
+    assert b.pooled_contexts == 1
+
+    slot = (16 << 20) + (16 << 20) // 512 * 4
+    assert slot == (16 << 20) + (128 << 10)
+    print("pinned", a.pinned_bytes, b.pinned_bytes, "device", a.device_bytes, b.device_bytes)
+    assert b.pinned_bytes - a.pinned_bytes == slot
+    assert b.device_bytes - a.device_bytes == slot
+
+    assert lib.hdfs3_crc_pool_trim() == 1
+    z = stats()
+    assert z.pooled_contexts == 0 and z.pinned_bytes == 0 and z.device_bytes == 0
