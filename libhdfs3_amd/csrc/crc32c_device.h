@@ -1,6 +1,8 @@
 // Device code of the gfx950 CRC32C kernels and their launch templates, shared by the
 // production translation unit (crc32c_kernels.hip) and the A/B experiments
-// (crc32c_experiments.hip). Internal; not installed.
+// (crc32c_experiments.hip): the table image and its lookups, the chunk-per-lane, multi-round and packet
+// kernels, the pieces of the round kernel (crc32c_wave.h). No lab code (clock stamps: crc32c_lab.h; read
+// ceilings: crc32c_experiments.hip): it reads the same in both builds. Internal; not installed.
 #pragma once
 // gfx950 (CDNA4) CRC32C kernels for libhdfs3's per-chunk checksum path.
 //
@@ -179,89 +181,32 @@ __device__ __forceinline__ void store_be32(uint8_t *p, uint32_t v, bool aligned4
     p[0] = uint8_t(v >> 24); p[1] = uint8_t(v >> 16); p[2] = uint8_t(v >> 8); p[3] = uint8_t(v);
 }
 
-// Main chunk kernel. BPC > 0: compile-time bytes-per-checksum (512/1024/2048/4096)
-// with 16-byte aligned data; BPC == 0: run-time bpc / any alignment.
-//
-// Each lane streams its chunk as 128-byte lines (8 x global_load_dwordx4): the
-// loads of line l+1 (or of the next chunk's first line) are issued, and pinned
-// in place by a sched_barrier, before line l is consumed, so every lane keeps
-// 128-256 B in flight (256 KiB per CU) while it works through the tables.
-template <int BPC, bool VERIFY>
-__global__ __launch_bounds__(kBlockThreads) void crc32c_chunks_kernel(ChunkLaunch a,
-                                                                      const uint32_t *__restrict__ g_tab) {
+// Chunk-per-lane kernel (crc_run_any): run-time bpc, any alignment, short blocks, a launch's short last chunk
+template <bool VERIFY>
+__global__ __launch_bounds__(kBlockThreads) void crc32c_chunks_kernel(ChunkLaunch a, const uint32_t *__restrict__ g_tab) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsBytes / 4];
-    const uint32_t bpc = BPC > 0 ? uint32_t(BPC) : a.bpc;
+    const uint32_t bpc = a.bpc;
     const uint64_t nfull = a.len / bpc;
     const uint64_t stride = uint64_t(gridDim.x) * kBlockThreads;
     uint64_t chunk = uint64_t(blockIdx.x) * kBlockThreads + threadIdx.x;
     const bool crc_al4 = (reinterpret_cast<uintptr_t>(VERIFY ? a.crc_be : a.out_be) & 3u) == 0;
 
-    u32x4 cur[8];
-    uint32_t tv[kFillPerThread];
-    fetch_tables(tv, g_tab);
-    if constexpr (BPC > 0) {
-        // First line in flight before the table fill so HBM latency overlaps it.
-        // Unconditional (idle lanes re-read the last chunk; host ensures nfull >= 1)
-        // so the waitcnt pass can count it precisely and not drain it at the fill.
-        const uint64_t first = chunk < nfull ? chunk : nfull - 1;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) cur[i] = ld16(a.data + first * BPC + 16 * i);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    store_tables(lds, tv);
+    fill_tables(lds, g_tab);
     lds_barrier();
     const Lut t(lds);
 
     for (; chunk < nfull; chunk += stride) {
         const uint8_t *p = a.data + chunk * bpc;
-        uint32_t c;
-        // Stored word requested first: it is older than the prefetches below, so
-        // waiting for it never drains the next chunk's loads (vmcnt is in-order).
+        // Stored word requested first: it is older than the chunk's loads, so
+        // waiting for it never drains them (vmcnt is in-order).
         uint32_t want = 0;
+        if constexpr (VERIFY) want = load_be32(a.crc_be + 4 * chunk, crc_al4);
+        const uint32_t c = ~crc_run_any(t, 0xFFFFFFFFu, p, bpc);
         if constexpr (VERIFY) {
-            if constexpr (BPC > 0)  // fast path: host guarantees a 4-byte aligned CRC array
-                want = *reinterpret_cast<const uint32_t *>(a.crc_be + 4 * chunk);
-            else
-                want = load_be32(a.crc_be + 4 * chunk, crc_al4);
-        }
-        if constexpr (BPC > 0) {
-            constexpr int kLines = BPC / 128;
-            const uint64_t next_chunk = chunk + stride;
-            // Last line prefetches the next chunk's first line; with no next chunk
-            // it re-reads this chunk's (cache-resident) first line instead of
-            // branching, so the load set stays unconditional and register-renamed.
-            const uint8_t *pnext = next_chunk < nfull ? a.data + next_chunk * BPC : p;
-            uint32_t x = 0xFFFFFFFFu ^ cur[0].x;
-#pragma unroll
-            for (int l = 0; l < kLines; ++l) {
-                u32x4 nxt[8];
-                const uint8_t *src = l + 1 < kLines ? p + 128 * (l + 1) : pnext;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) nxt[i] = ld16(src + 16 * i);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    x = t.word(x, cur[i].y);
-                    x = t.word(x, cur[i].z);
-                    x = t.word(x, cur[i].w);
-                    const uint32_t follow = i < 7 ? cur[i + 1 < 8 ? i + 1 : 7].x
-                                                  : (l + 1 < kLines ? nxt[0].x : 0u);
-                    x = t.word(x, follow);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) cur[i] = nxt[i];
-            }
-            c = x;
-        } else {
-            c = crc_run_any(t, 0xFFFFFFFFu, p, bpc);
-        }
-        c = ~c;
-        if constexpr (VERIFY) {
-            if (BPC > 0) want = __builtin_bswap32(want);
             if (want != c)
                 atomicMax(a.result, ~(unsigned long long)(a.chunk_base + chunk));
         } else {
-            store_be32(a.out_be + 4 * chunk, c, BPC > 0 || crc_al4);
+            store_be32(a.out_be + 4 * chunk, c, crc_al4);
         }
     }
     // The lane whose stride sequence lands exactly on nfull owns the short tail chunk.
@@ -302,12 +247,10 @@ struct Round {
     uint32_t w[4][4];  // [load register][dword]
 };
 
-template <bool NT = false>
 __device__ __forceinline__ void load_round(Round &r, const uint8_t *base, uint32_t lane_off) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const u32x4 v = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(base + 1024 * t + lane_off))
-                           : ld16(base + 1024 * t + lane_off);
+        const u32x4 v = ld16(base + 1024 * t + lane_off);
         r.w[t][0] = v.x;
         r.w[t][1] = v.y;
         r.w[t][2] = v.z;
@@ -329,8 +272,7 @@ __device__ __forceinline__ uint64_t rfl64(uint64_t x) {
 // temporaries exist that the allocator could alias with in-flight load destinations
 // (which made the compiler drain the previous round's loads before each prefetch).
 // nb: the round's valid bytes (the resource's range; a partial round's lanes past it load zeros
-// without touching memory)
-template <bool NT>
+// without touching memory). Non-temporal loads (nt): a round is read once
 __device__ __forceinline__ void load_round_buf(Round &r, const uint8_t *base, uint32_t lane_off, uint32_t nb = 4096) {
     const uint64_t b = reinterpret_cast<uint64_t>(base);
     const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(b));
@@ -339,7 +281,7 @@ __device__ __forceinline__ void load_round_buf(Round &r, const uint8_t *base, ui
         reinterpret_cast<void *>((uint64_t(hi) << 32) | lo), 0, __builtin_amdgcn_readfirstlane(nb), 0x00020000);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off + 1024 * t, 0, NT ? 2 : 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off + 1024 * t, 0, 2);
         r.w[t][0] = v.x;
         r.w[t][1] = v.y;
         r.w[t][2] = v.z;
@@ -423,20 +365,19 @@ __device__ __forceinline__ uint32_t group_xor(uint32_t v) {
     return v;
 }
 
-template <int BPC, bool VERIFY, int DEPTH, bool FOLD4, bool PRIO = false>
+// The multi-round kernel: chunks of R = BPC / 4096 whole rounds (8 / 16 / 64 KiB below kPiecesMinBytes per
+// launch). A wave's unit is one chunk: its rounds in order, one in flight beside the one it consumes, each
+// folded with the G = 64 lane-fold columns, the chunk's running state advanced by the 4096-byte matrix.
+template <int BPC, bool VERIFY, bool PRIO = false>
 __global__ __launch_bounds__(kBlockThreads) void crc32c_rounds_kernel(ChunkLaunch a,
                                                                       const uint32_t *__restrict__ g_tab,
                                                                       const uint32_t *__restrict__ g_fold) {
+    static_assert(BPC > kRoundBytes && BPC % kRoundBytes == 0, "chunks of two or more whole rounds");
     __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsBytes / 4];
-    constexpr int kUnit = BPC <= kRoundBytes ? kRoundBytes : BPC;  // bytes per wave work unit
-    constexpr int kRoundsPerUnit = kUnit / kRoundBytes;
-    constexpr int G = BPC <= kRoundBytes ? BPC / 64 : 64;           // lanes per chunk in a round
-    constexpr int kChunksPerUnit = BPC <= kRoundBytes ? kRoundBytes / BPC : 1;
-    constexpr int kFoldSet = G == 8 ? 0 : G == 16 ? 1 : G == 32 ? 2 : 3;
-    constexpr int kFoldOff[4] = {0, 8, 24, 56};
+    constexpr int kUnit = BPC, kRoundsPerUnit = kUnit / kRoundBytes;  // a wave's work unit: one chunk
+    constexpr int G = 64, kFoldOff = 56;  // lanes per chunk in a round; their columns (crc32c_tables.h: kFoldOffset[3])
 
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t j = lane % G;
+    const uint32_t lane = threadIdx.x & 63, j = lane;
     const uint32_t lane_off = 64 * (lane & 15) + 16 * (lane >> 4);
     const uint64_t nunits = a.len / kUnit;
     const uint64_t nwaves = uint64_t(gridDim.x) * kWavesPerBlock;
@@ -453,36 +394,34 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_rounds_kernel(ChunkLaunc
         return a.data + (wave + (kk / kRoundsPerUnit) * nwaves) * kUnit + (kk % kRoundsPerUnit) * kRoundBytes;
     };
 
-    // small cache-resident reads first (tables, fold columns), then the first two
-    // rounds: the in-order vmcnt then lets the table fill proceed while rounds land
+    // small cache-resident reads first (tables, fold columns), then the first
+    // round: the in-order vmcnt then lets the table fill proceed while rounds land
     uint32_t col[32];
 #pragma unroll
-    for (int i = 0; i < 32; ++i) col[i] = g_fold[(kFoldOff[kFoldSet] + j) * 32 + i];
+    for (int i = 0; i < 32; ++i) col[i] = g_fold[(kFoldOff + j) * 32 + i];
     uint32_t tv[kFillPerThread];
     fetch_tables(tv, g_tab);
     __builtin_amdgcn_sched_barrier(0);
-    Round b0, b1, b2;
+    Round b0, b1;
     load_round(b0, round_ptr(0), lane_off);
-    if constexpr (DEPTH == 2) load_round(b1, round_ptr(1), lane_off);
     __builtin_amdgcn_sched_barrier(0);
     store_tables(lds, tv);
     lds_barrier();
     const Lut t(lds);
 
     uint32_t acc = 0;
-    // One round: issue the stored CRC word and the prefetch of round k+DEPTH into
+    // One round: issue the stored CRC word and the prefetch of round k+1 into
     // `pf`, then consume `cur`.
     auto step = [&](Round &cur, Round &pf, uint64_t k) {
         const uint32_t r = uint32_t(k % kRoundsPerUnit);
-        const uint64_t unit = wave + (k / kRoundsPerUnit) * nwaves;
-        const uint64_t chunk = unit * kChunksPerUnit + lane / G;
+        const uint64_t chunk = wave + (k / kRoundsPerUnit) * nwaves;  // the wave's unit is one chunk
         uint32_t want = 0;
         if constexpr (VERIFY) {
             // every lane of a chunk reads its word (one broadcast access), issued before
             // the prefetch so that waiting for it never drains the prefetch (vmcnt is in-order)
             want = *reinterpret_cast<const uint32_t *>(a.crc_be + 4 * chunk);
         }
-        load_round(pf, round_ptr(k + DEPTH), lane_off);
+        load_round(pf, round_ptr(k + 1), lane_off);
         __builtin_amdgcn_sched_barrier(0);
         regroup(cur);
         uint32_t x = ((j == 0 && r == 0) ? 0xFFFFFFFFu : 0u) ^ cur.w[0][0];
@@ -493,14 +432,12 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_rounds_kernel(ChunkLaunc
             x = t.word(x, cur.w[q][3]);
             x = t.word(x, q < 3 ? cur.w[q < 3 ? q + 1 : 3][0] : 0u);
         }
-        uint32_t y = group_xor<G>(FOLD4 ? gf2_apply4(col, x) : gf2_apply(col, x));
-        if constexpr (kRoundsPerUnit > 1) {
-            if (r > 0) {
-                uint32_t k4096[32];
+        uint32_t y = group_xor<G>(gf2_apply4(col, x));
+        if (r > 0) {
+            uint32_t k4096[32];
 #pragma unroll
-                for (int i = 0; i < 32; ++i) k4096[i] = g_fold[kFoldAdvance4096 + i];
-                y ^= gf2_apply(k4096, acc);
-            }
+            for (int i = 0; i < 32; ++i) k4096[i] = g_fold[kFoldAdvance4096 + i];
+            y ^= gf2_apply(k4096, acc);
         }
         acc = y;
         if (r == kRoundsPerUnit - 1 && j == 0) {
@@ -526,29 +463,19 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_rounds_kernel(ChunkLaunc
             else __builtin_amdgcn_s_setprio(0);
         }
     };
-    // (DEPTH+1)-buffer ring unrolled so the buffers rotate by renaming (a loop-carried
+    // two buffers unrolled so they rotate by renaming (a loop-carried
     // register copy would make the compiler wait for the youngest prefetch)
-    if constexpr (DEPTH == 2) {
-        for (uint64_t k = 0; k < K; k += 3) {
-            step(b0, b2, k);
-            if (k + 1 >= K) break;
-            step(b1, b0, k + 1);
-            if (k + 2 >= K) break;
-            step(b2, b1, k + 2);
-        }
-    } else {
-        for (uint64_t k = 0; k < K; k += 2) {
-            prio(k);
-            step(b0, b1, k);
-            if (k + 1 >= K) break;
-            step(b1, b0, k + 1);
-        }
+    for (uint64_t k = 0; k < K; k += 2) {
+        prio(k);
+        step(b0, b1, k);
+        if (k + 1 >= K) break;
+        step(b1, b0, k + 1);
     }
 
     // Slow region: chunks after the last whole unit, plus the short tail chunk, one
     // lane per chunk (at most a unit's worth, so a handful of lanes).
     const uint64_t nfull = a.len / BPC;
-    const uint64_t first_slow = nunits * kChunksPerUnit;
+    const uint64_t first_slow = nunits;
     const uint64_t nslow = nfull - first_slow + (a.len % BPC ? 1 : 0);
     const uint64_t gtid = uint64_t(blockIdx.x) * kBlockThreads + threadIdx.x;
     if (gtid < nslow) {
@@ -695,171 +622,18 @@ __global__ __launch_bounds__(kBlockThreads) void crc32c_packets_kernel(
     }
 }
 
-// ---- measurement-only kernels ------------------------------------------------
-
-// Coalesced streaming read (1 KiB per wave-instruction): the achievable HBM read
-// ceiling the CRC kernel is compared with.
-#if HDFS3_LAB
-// Lab-only clock stamps (hdfs3x_clock_stamps, tools/clock_ramp.py): thread 0 of workgroup 0 of every
-// launch of a stamping kernel records {s_memtime, s_memrealtime} at its start and end into the next
-// slot of g_lab_clk (4 words per launch). s_memtime counts the shader clock and s_memrealtime a fixed
-// 100 MHz, so the ratio of their deltas is the shader clock over that workgroup's lifetime. Vector
-// stores and a vector atomic only; nothing when no buffer is set.
-// With a wave buffer installed (hdfs3x_wave_stamps, tools/wave_spread.py) lane 0 of EVERY wave also
-// records {realtime start, realtime end, shader clocks elapsed, HW_ID | XCC_ID << 32 | wave << 36 |
-// launch << 52}:
-// where each launch's time goes between its first wave's start and its last wave's end.
-__device__ unsigned long long *g_lab_clk = nullptr;
-__device__ unsigned int g_lab_clk_cap = 0;
-__device__ unsigned int g_lab_clk_n = 0;
-__device__ unsigned long long *g_lab_wave = nullptr;
-__device__ unsigned int g_lab_wave_cap = 0;
-struct LabClock {
-    unsigned long long t0 = 0, r0 = 0;
-    __device__ __forceinline__ void start() {
-        if ((threadIdx.x & 63) == 0) {
-            t0 = __builtin_amdgcn_s_memtime();
-            r0 = __builtin_amdgcn_s_memrealtime();
-        }
-    }
-    // seq: the launch's number (host counter g_lab_seq): wave w of launch seq owns slot
-    // (seq * waves + w) % cap, so no two waves meet on an atomic (a shared counter serialised
-    // 4,096 waves per launch and stretched a 128 MiB launch 8x)
-    // word2: what word 2 of the wave's stamp holds (default: the shader clocks of its life)
-    __device__ __forceinline__ void end(uint32_t seq = 0, unsigned long long word2 = ~0ull) {
-        if ((threadIdx.x & 63) != 0) return;
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (blockIdx.x == 0 && threadIdx.x == 0 && g_lab_clk) {
-            const unsigned int i = atomicAdd(&g_lab_clk_n, 1u);
-            if (i < g_lab_clk_cap) {
-                g_lab_clk[4 * i] = t0;
-                g_lab_clk[4 * i + 1] = r0;
-                g_lab_clk[4 * i + 2] = t1;
-                g_lab_clk[4 * i + 3] = r1;
-            }
-        }
-        if (g_lab_wave) {
-            // HW_ID (hwreg 4, 32 bits: wave/simd/cu/sh/se) and XCC_ID (hwreg 20, low 4 bits)
-            const unsigned long long hw = uint32_t(__builtin_amdgcn_s_getreg((31 << 11) | 4));
-            const unsigned long long xcc = uint32_t(__builtin_amdgcn_s_getreg((3 << 11) | 20));
-            const uint64_t wpl = uint64_t(gridDim.x) * (blockDim.x / 64);
-            const uint64_t wv = uint64_t(blockIdx.x) * (blockDim.x / 64) + threadIdx.x / 64;
-            const uint64_t i = (uint64_t(seq) * wpl + wv) % g_lab_wave_cap;
-            g_lab_wave[4 * i] = r0;
-            g_lab_wave[4 * i + 1] = r1;
-            g_lab_wave[4 * i + 2] = word2 == ~0ull ? t1 - t0 : word2;
-            g_lab_wave[4 * i + 3] = hw | (xcc & 15) << 32 | (wv & 0xFFFF) << 36 | uint64_t(seq & 0xFFF) << 52;
-        }
-    }
-};
-#endif
-
-template <bool NT>
-__global__ __launch_bounds__(256) void stream_read_kernel(const uint8_t *__restrict__ d,
-                                                          uint64_t n16, uint32_t *sink, uint32_t seq) {
-    auto ld = [](const uint8_t *p) -> u32x4 {
-        if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
-        return ld16(p);
-    };
-#if HDFS3_LAB
-    LabClock clk;
-    clk.start();
-#endif
-    uint32_t acc = 0;
-    const uint64_t stride = uint64_t(gridDim.x) * 256;
-    uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
-    for (; i + 3 * stride < n16; i += 4 * stride) {
-        const u32x4 a = ld(d + 16 * i), b = ld(d + 16 * (i + stride));
-        const u32x4 c = ld(d + 16 * (i + 2 * stride)), e = ld(d + 16 * (i + 3 * stride));
-        acc ^= a.x ^ a.y ^ a.z ^ a.w ^ b.x ^ b.y ^ b.z ^ b.w ^ c.x ^ c.y ^ c.z ^ c.w ^ e.x ^ e.y ^
-               e.z ^ e.w;
-    }
-    for (; i < n16; i += stride) {
-        const u32x4 a = ld(d + 16 * i);
-        acc ^= a.x ^ a.y ^ a.z ^ a.w;
-    }
-    if (acc == 0x9E3779B9u) sink[0] = acc;  // keep the loads live
-#if HDFS3_LAB
-    clk.end(seq);
-#else
-    (void)seq;
-#endif
-}
-
-// Access-pattern probes (xor instead of table arithmetic), selected by `variant`:
-//  0: chunk per lane, 8 x 16 B per 128 B line, nt loads   (the v1 CRC kernel's pattern)
-//  1: same, default cache policy
-//  2: G=8 lanes per chunk, one full 128 B line per chunk per instruction (coalesced)
-//  3: G=4 lanes per chunk, 64 B per chunk per instruction
-//  4: chunk per lane, 2 x 16 B (32 B) per lane per instruction pair, lines split over 4 lanes
-template <int BPC, int VARIANT>
-__global__ __launch_bounds__(kBlockThreads) void lane_read_kernel(const uint8_t *__restrict__ d,
-                                                                  uint64_t nchunks, uint32_t *sink) {
-    uint32_t acc = 0;
-    const uint64_t tid = uint64_t(blockIdx.x) * kBlockThreads + threadIdx.x;
-    const uint64_t nthreads = uint64_t(gridDim.x) * kBlockThreads;
-    if constexpr (VARIANT <= 1) {
-        for (uint64_t chunk = tid; chunk < nchunks; chunk += nthreads) {
-            const uint8_t *p = d + chunk * BPC;
-#pragma unroll
-            for (int l = 0; l < BPC / 128; ++l) {
-                u32x4 v[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const u32x4 *q = reinterpret_cast<const u32x4 *>(p + 128 * l + 16 * i);
-                    v[i] = VARIANT == 0 ? __builtin_nontemporal_load(q) : *q;
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc = (acc ^ v[i].x ^ v[i].y ^ v[i].z ^ v[i].w) * 3u;
-            }
-        }
-    } else if constexpr (VARIANT == 2 || VARIANT == 3) {
-        constexpr int G = VARIANT == 2 ? 8 : 4;
-        const uint64_t groups = nthreads / G;
-        for (uint64_t chunk = tid / G; chunk < nchunks; chunk += groups) {
-            const uint8_t *p = d + chunk * BPC + 16 * (tid % G);
-            constexpr int N = BPC / (16 * G), U = N < 8 ? N : 8;
-#pragma unroll
-            for (int t0 = 0; t0 < N; t0 += U) {
-                u32x4 v[U];
-#pragma unroll
-                for (int i = 0; i < U; ++i) v[i] = *reinterpret_cast<const u32x4 *>(p + 16 * G * (t0 + i));
-#pragma unroll
-                for (int i = 0; i < U; ++i) acc = (acc ^ v[i].x ^ v[i].y ^ v[i].z ^ v[i].w) * 3u;
-            }
-        }
-    } else {
-        for (uint64_t chunk = tid; chunk < nchunks; chunk += nthreads) {
-            const uint8_t *p = d + chunk * BPC;
-#pragma unroll
-            for (int l = 0; l < BPC / 128; ++l) {
-                u32x4 v[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const u32x4 *>(p + 128 * l + 16 * ((i * 2) % 8 + (i / 4)));
-#pragma unroll
-                for (int i = 0; i < 8; ++i) acc = (acc ^ v[i].x ^ v[i].y ^ v[i].z ^ v[i].w) * 3u;
-            }
-        }
-    }
-    if (acc == 0x9E3779B9u) sink[0] = acc;
-}
-
-template <int BPC, bool V>
+template <bool V>
 hipError_t launch_t(const ChunkLaunch &a, const uint32_t *tab, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((crc32c_chunks_kernel<BPC, V>), dim3(grid), dim3(kBlockThreads), 0, s, a,
-                       tab);
+    hipLaunchKernelGGL((crc32c_chunks_kernel<V>), dim3(grid), dim3(kBlockThreads), 0, s, a, tab);
     return hipGetLastError();
 }
 
-template <int BPC, bool V, int DEPTH, bool FOLD4, bool PRIO = false>
-hipError_t launch_r3(const ChunkLaunch &a, const uint32_t *tab, const uint32_t *fold, int grid_cap,
-                     hipStream_t s) {
-    constexpr uint64_t kUnit = BPC <= kRoundBytes ? kRoundBytes : BPC;
-    const uint64_t units = a.len / kUnit;
+template <int BPC, bool V, bool PRIO = false>
+hipError_t launch_r3(const ChunkLaunch &a, const uint32_t *tab, const uint32_t *fold, int grid_cap, hipStream_t s) {
+    const uint64_t units = a.len / BPC;
     const uint64_t need = (units + kWavesPerBlock - 1) / kWavesPerBlock;
     const int grid = int(need < uint64_t(grid_cap) ? need : uint64_t(grid_cap));
-    hipLaunchKernelGGL((crc32c_rounds_kernel<BPC, V, DEPTH, FOLD4, PRIO>), dim3(grid), dim3(kBlockThreads), 0, s,
-                       a, tab, fold);
+    hipLaunchKernelGGL((crc32c_rounds_kernel<BPC, V, PRIO>), dim3(grid), dim3(kBlockThreads), 0, s, a, tab, fold);
     return hipGetLastError();
 }
 

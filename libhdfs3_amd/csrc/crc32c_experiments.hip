@@ -1,5 +1,6 @@
 // Kernel variants kept for in-process A/B and diagnostics (hdfs3x_set_variant, tools/ab.py;
-// docs/DESIGN_HISTORY.md §5.0), and the read-ceiling kernels of the bench. Linked into the measurement
+// docs/DESIGN_HISTORY.md §5.0), the read-ceiling and access-pattern kernels of the bench
+// (stream_read_kernel, lane_read_kernel), the clock stamps' host side (crc32c_lab.h). Linked into the measurement
 // library libhdfs3_crc_lab.so only (HDFS3_LAB=1); the product libhdfs3_crc.so never sees it.
 // Bit-exact variants are parity-tested (tests/test_gpu_parity.py); the diagnostic one gives
 // wrong results on purpose. The designs that lost their A/B were removed in round 3; their
@@ -13,12 +14,100 @@
 namespace hdfs3crc {
 namespace {
 
+// ---- measurement-only kernels ------------------------------------------------
+
+// Coalesced streaming read (1 KiB per wave-instruction): the achievable HBM read
+// ceiling the CRC kernel is compared with.
+template <bool NT>
+__global__ __launch_bounds__(256) void stream_read_kernel(const uint8_t *__restrict__ d,
+                                                          uint64_t n16, uint32_t *sink, uint32_t seq) {
+    auto ld = [](const uint8_t *p) -> u32x4 {
+        if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
+        return ld16(p);
+    };
+    LabClock clk;
+    clk.start();
+    uint32_t acc = 0;
+    const uint64_t stride = uint64_t(gridDim.x) * 256;
+    uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+    for (; i + 3 * stride < n16; i += 4 * stride) {
+        const u32x4 a = ld(d + 16 * i), b = ld(d + 16 * (i + stride));
+        const u32x4 c = ld(d + 16 * (i + 2 * stride)), e = ld(d + 16 * (i + 3 * stride));
+        acc ^= a.x ^ a.y ^ a.z ^ a.w ^ b.x ^ b.y ^ b.z ^ b.w ^ c.x ^ c.y ^ c.z ^ c.w ^ e.x ^ e.y ^
+               e.z ^ e.w;
+    }
+    for (; i < n16; i += stride) {
+        const u32x4 a = ld(d + 16 * i);
+        acc ^= a.x ^ a.y ^ a.z ^ a.w;
+    }
+    if (acc == 0x9E3779B9u) sink[0] = acc;  // keep the loads live
+    clk.end(seq);
+}
+
+// Access-pattern probes (xor instead of table arithmetic), selected by `variant`:
+//  0: chunk per lane, 8 x 16 B per 128 B line, nt loads   (the v1 CRC kernel's pattern)
+//  1: same, default cache policy
+//  2: G=8 lanes per chunk, one full 128 B line per chunk per instruction (coalesced)
+//  3: G=4 lanes per chunk, 64 B per chunk per instruction
+//  4: chunk per lane, 2 x 16 B (32 B) per lane per instruction pair, lines split over 4 lanes
+template <int BPC, int VARIANT>
+__global__ __launch_bounds__(kBlockThreads) void lane_read_kernel(const uint8_t *__restrict__ d,
+                                                                  uint64_t nchunks, uint32_t *sink) {
+    uint32_t acc = 0;
+    const uint64_t tid = uint64_t(blockIdx.x) * kBlockThreads + threadIdx.x;
+    const uint64_t nthreads = uint64_t(gridDim.x) * kBlockThreads;
+    if constexpr (VARIANT <= 1) {
+        for (uint64_t chunk = tid; chunk < nchunks; chunk += nthreads) {
+            const uint8_t *p = d + chunk * BPC;
+#pragma unroll
+            for (int l = 0; l < BPC / 128; ++l) {
+                u32x4 v[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const u32x4 *q = reinterpret_cast<const u32x4 *>(p + 128 * l + 16 * i);
+                    v[i] = VARIANT == 0 ? __builtin_nontemporal_load(q) : *q;
+                }
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc = (acc ^ v[i].x ^ v[i].y ^ v[i].z ^ v[i].w) * 3u;
+            }
+        }
+    } else if constexpr (VARIANT == 2 || VARIANT == 3) {
+        constexpr int G = VARIANT == 2 ? 8 : 4;
+        const uint64_t groups = nthreads / G;
+        for (uint64_t chunk = tid / G; chunk < nchunks; chunk += groups) {
+            const uint8_t *p = d + chunk * BPC + 16 * (tid % G);
+            constexpr int N = BPC / (16 * G), U = N < 8 ? N : 8;
+#pragma unroll
+            for (int t0 = 0; t0 < N; t0 += U) {
+                u32x4 v[U];
+#pragma unroll
+                for (int i = 0; i < U; ++i) v[i] = *reinterpret_cast<const u32x4 *>(p + 16 * G * (t0 + i));
+#pragma unroll
+                for (int i = 0; i < U; ++i) acc = (acc ^ v[i].x ^ v[i].y ^ v[i].z ^ v[i].w) * 3u;
+            }
+        }
+    } else {
+        for (uint64_t chunk = tid; chunk < nchunks; chunk += nthreads) {
+            const uint8_t *p = d + chunk * BPC;
+#pragma unroll
+            for (int l = 0; l < BPC / 128; ++l) {
+                u32x4 v[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const u32x4 *>(p + 128 * l + 16 * ((i * 2) % 8 + (i / 4)));
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc = (acc ^ v[i].x ^ v[i].y ^ v[i].z ^ v[i].w) * 3u;
+            }
+        }
+    }
+    if (acc == 0x9E3779B9u) sink[0] = acc;
+}
+
 template <int BPC, bool V>
 hipError_t launch_exp(const LaunchEnv &env, int variant, const ChunkLaunch &a) {
     const auto [tab, fold, grid_cap, s] = std::tie(env.tables, env.fold, env.grid_cap, env.stream);
     if constexpr (BPC > kRoundBytes) {
-        if (variant == 115) return launch_r3<BPC, V, 1, true, true>(a, tab, fold, grid_cap, s);  // s_setprio
-        if (variant == 123) return launch_r3<BPC, V, 1, true>(a, tab, fold, grid_cap, s);  // multi-round kernel
+        if (variant == 115) return launch_r3<BPC, V, true>(a, tab, fold, grid_cap, s);  // s_setprio
+        if (variant == 123) return launch_r3<BPC, V>(a, tab, fold, grid_cap, s);  // multi-round kernel
     }
     if constexpr (BPC <= kRoundBytes) {
         switch (variant) {
@@ -28,7 +117,7 @@ hipError_t launch_exp(const LaunchEnv &env, int variant, const ChunkLaunch &a) {
             return launch_wave3<BPC, V, false, false>(a, tab, fold, grid_cap, s);
         case 94:  // the solo last step for overlapped verifies only (round-3 production before r3i)
             return launch_wave3<BPC, V, false, V>(a, tab, fold, grid_cap, s);
-        case 95:  // compute at bpc 512 / 4096 without held stores (each round's words stored at once)
+        case 95:  // compute: each round's words stored at once everywhere (Words::kPerRound)
             return launch_wave3<BPC, V, false, true, kLabNoHold>(a, tab, fold, grid_cap, s);
         case 77:  // diagnostic: production with the table lookups replaced by an XOR (wrong results)
             return launch_wave3<BPC, V, false, true, kLabNoMath>(a, tab, fold, grid_cap, s);
@@ -60,8 +149,6 @@ hipError_t launch_exp(const LaunchEnv &env, int variant, const ChunkLaunch &a) {
             return launch_wave3<BPC, V, false, true, kLabNoStage>(a, tab, fold, grid_cap, s);
         case 130:  // compute: staged words at every size, written out window by window (kLabStageWin)
             return launch_wave3<BPC, V, false, true, kLabStageWin>(a, tab, fold, grid_cap, s);
-        case 157:  // the round-4 chains (16 table steps, the fold on the finished state; kLabFull16)
-            return launch_wave3<BPC, V, false, true, kLabFull16>(a, tab, fold, grid_cap, s);
         case 128:  // compute: staged words through plain global stores (production before round 4)
             return launch_wave3<BPC, V, false, true, kLabStorePlain>(a, tab, fold, grid_cap, s);
         case 146:  // production with every wave's fill-done and first-data times (wave_spread.py --variant 146 --mid)

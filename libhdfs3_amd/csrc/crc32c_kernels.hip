@@ -1,6 +1,6 @@
 // gfx950 (CDNA4) CRC32C kernels for libhdfs3's per-chunk checksum path: production launchers.
-// The device code (kernels, design notes) is in crc32c_device.h; the kernel variants kept for
-// A/B are in crc32c_experiments.hip; which launcher a batch takes is decided in launch_plan.cpp.
+// The device code (kernels, design notes) is in crc32c_device.h and crc32c_wave.h; the kernel variants
+// kept for A/B are in crc32c_experiments.hip; which launcher a batch takes is decided in launch_plan.cpp.
 #include "crc32c_wave.h"
 
 namespace hdfs3crc {
@@ -25,7 +25,8 @@ hipError_t launch_r(const LaunchEnv &env, const ChunkLaunch &a) {
 #endif
     if constexpr (BPC <= kRoundBytes)
         return launch_wave3<BPC, V, false, true>(a, env.tables, env.fold, env.grid_cap, env.stream);
-    return launch_r3<BPC, V, 1, true>(a, env.tables, env.fold, env.grid_cap, env.stream);
+    else
+        return launch_r3<BPC, V>(a, env.tables, env.fold, env.grid_cap, env.stream);
 }
 
 // packet streams at a constant pitch: the production round kernel's pitch walk
@@ -41,7 +42,7 @@ hipError_t launch_p(const LaunchEnv &env, const ChunkLaunch &a) {
     if (g_variant == 132) return launch_wave3<BPC, V, true, true, 0, 256>(a, tab, fold, grid_cap, s);
     if (g_variant == 134) return launch_wave3<BPC, V, true, true, 0, 512>(a, tab, fold, grid_cap, s);
     if (g_variant == 137) return launch_wave3<BPC, V, true, true, kLabWg1024>(a, tab, fold, grid_cap, s);
-    // compute: each round's words stored at once instead of held (round 6, the writer's small batches)
+    // compute: each round's words stored at once at every size (round 6, the writer's small batches)
     if (g_variant == 163) return launch_wave3<BPC, V, true, true, kLabNoHold>(a, tab, fold, grid_cap, s);
     // one round per wave for launches of <= 4096 units (round 6)
     if (g_variant == 162) return launch_wave3<BPC, V, true, true, kLabOneRound>(a, tab, fold, grid_cap, s);
@@ -191,7 +192,7 @@ hipError_t launch_tail_chunk(const LaunchEnv &env, const ChunkLaunch &a, bool ve
     t.result = a.result;
     if (verify) t.crc_be = a.crc_be + word;
     else t.out_be = a.out_be + word;
-    return verify ? launch_t<0, true>(t, env.tables, 1, env.stream) : launch_t<0, false>(t, env.tables, 1, env.stream);
+    return verify ? launch_t<true>(t, env.tables, 1, env.stream) : launch_t<false>(t, env.tables, 1, env.stream);
 }
 
 // Whole chunks of R = bpc / 4096 pieces: the round kernel's compute at bpc 4096 into the scratch,
@@ -305,8 +306,8 @@ hipError_t launch_chunks(const LaunchEnv &env, const ChunkLaunch &a, bool verify
             return verify ? launch_r<bpc(), true>(env, a) : launch_r<bpc(), false>(env, a);
         });
     const int grid = clamped_grid((chunks + kBlockThreads - 1) / kBlockThreads, uint64_t(env.grid_cap));
-    return verify ? launch_t<0, true>(a, env.tables, grid, env.stream)
-                  : launch_t<0, false>(a, env.tables, grid, env.stream);
+    return verify ? launch_t<true>(a, env.tables, grid, env.stream)
+                  : launch_t<false>(a, env.tables, grid, env.stream);
 }
 
 hipError_t launch_packets(const LaunchEnv &env, const uint8_t *d_arena, const DevPacket *d_pk, uint64_t n,

@@ -75,22 +75,12 @@ inline void build_fold_matrices(const uint32_t t0[kTableEntries], uint32_t out[k
     shift_cols(t0, 4096, out + kFoldAdvance4096);
 }
 
-// Lane-specific fold as LDS nibble tables (the round kernels' fold): for each of the
-// 64 lanes of a wave, lane j = lane % G, nibble k (0..7) and value e (0..15), the entry
-// M_j(e << 4k). Word index ((k * 16 + e) * 64 + lane): every lane reads its own bank.
+// Lane-specific fold as LDS nibble tables (the round kernel's fold): for each of the
+// 64 lanes of a wave, lane j = lane % G, nibble k (0..7) and value e (0..15), an entry
+// for e << 4k. Word index ((k * 16 + e) * 64 + lane): every lane reads its own bank.
 constexpr int kFoldNibbleWords = 8 * 16 * 64;  // 32 KiB per G
 
-inline void build_fold_nibbles(const uint32_t fold[kFoldWords], int set, uint32_t out[kFoldNibbleWords]) {
-    const int g = kFoldGs[set];
-    for (int lane = 0; lane < 64; ++lane) {
-        const uint32_t *cols = fold + (kFoldOffset[set] + lane % g) * 32;
-        for (int k = 0; k < 8; ++k)
-            for (uint32_t e = 0; e < 16; ++e)
-                out[(k * 16 + e) * 64 + lane] = apply_cols(cols, e << (4 * k));
-    }
-}
-
-// The round kernel's sets take a chain's state BEFORE its last word's table step (round 5): lane j's
+// The sets take a chain's state BEFORE its last word's table step (round 5): lane j's
 // 16-word chain ends in x = s ^ w15, whose finished state is T(x) (T = the 4-byte slice-by-4 step,
 // linear), so the entry M_j(T(e << 4k)) folds T into the lane fold and the kernel skips the last
 // word's 4 lookups (64 -> 60 slice lookups per lane and round).
@@ -115,9 +105,7 @@ inline void build_fold_nibbles_pre(const uint32_t t0[kTableEntries], const uint3
 // round to compare or store them).
 // The device fold image is the kFoldWords matrix columns followed by the 4 affine sets.
 constexpr int kFoldAffineOff = kFoldWords;
-// (lab A/B, round 5: the round-4 sets on the chain's finished state follow at kFoldAffineOldOff)
-constexpr int kFoldAffineOldOff = kFoldAffineOff + 4 * kFoldNibbleWords;
-constexpr int kFoldImageWords = kFoldAffineOldOff + 4 * kFoldNibbleWords;
+constexpr int kFoldImageWords = kFoldAffineOff + 4 * kFoldNibbleWords;
 // `out` holds set `set` built by build_fold_nibbles_pre; adds K_C in place
 inline void build_fold_affine(const uint32_t t0[kTableEntries], int set, uint32_t out[kFoldNibbleWords]) {
     const int g = kFoldGs[set];

@@ -25,36 +25,33 @@
 #pragma once
 
 #include "crc32c_device.h"
+#if HDFS3_LAB
+#include "crc32c_lab.h"  // LabClock: the stamping blocks of crc32c_wave_kernel
+#endif
 
 namespace hdfs3crc {
 namespace {
 
-// Lab-only bits of the round kernel (crc32c_experiments.hip; production passes 0):
+// Lab-only bits of the round kernel (crc32c_experiments.hip). Production passes 0: every kernel of the
+// product library has LAB = 0, and which word output a launch gets is words_policy's answer (launch_plan.h).
 constexpr int kLabEarly = 1;   // prefetch issued at the start of each step, not after its rounds landed
 constexpr int kLabNoMath = 2;  // diagnostic: table lookups replaced by an XOR of the words (wrong results)
-constexpr int kLabNoHold = 4;  // compute at bpc 512 / 4096: store each round's words at once (no held stores)
 constexpr int kLabNoFill = 8;  // diagnostic: the slice tables are not written to LDS (wrong results)
 constexpr int kLabPrio = 16;    // s_setprio by rounds left at every launch size (production: >= kPrioMinRounds)
 constexpr int kLabNoPrio = 32;  // no s_setprio at any launch size (the round-3 production before r3y)
-constexpr int kLabNoStore = 64;     // diagnostic, compute: the held words are not stored (wrong results)
+constexpr int kLabNoStore = 64;     // diagnostic, compute: the held / staged words are not stored (wrong results)
 constexpr int kLabNearStore = 128;  // diagnostic, compute: every flush stores to the wave's first round's words
-constexpr int kLabNoStage = 1024;   // compute: held stores even where production stages the words (kStageWords)
-constexpr int kLabStageWin = 2048;  // compute at bpc 512: staged words past kStageMaxRounds too, window by window
-constexpr int kLabClock = 4096;     // clock stamps of workgroup 0 (LabClock, crc32c_device.h; lab builds only)
+constexpr int kLabClock = 4096;     // clock stamps of workgroup 0 (LabClock, crc32c_lab.h; lab builds only)
 constexpr int kLabStorePlain = 8192;  // compute, staged words: plain global stores (production before round 4)
 constexpr int kLabWg1024 = 16384;    // verify: 1024-thread workgroups at every launch size (production before round 4)
 constexpr int kLabNoTabLoad = 2097152;  // diagnostic: the table images are not loaded (made up from t: wrong results)
-constexpr int kLabFull16 = 8388608;  // the round-4 chains: 16 table steps per chain, the fold on the finished state
 constexpr int kLabOneRound = 4194304;  // launches of <= 4096 units: one round per wave (twice the workgroups)
 constexpr int kLabMid = 1048576;     // with kLabClock: word 2 of a wave's stamp = fill done | first data << 21 | kernel
                                      // arguments landed << 42, each - start, 21 bits of 10 ns
-// Not a lab bit: launch_wave3 sets it for compute over a contiguous block at bpc 1024 / 2048, and at
-// bpc 512 when its waves have at most kStageMaxRounds(512) rounds (the words are staged in LDS and
-// written as whole lines, §4.1; past the window size in windows)
-constexpr int kStageWords = 512;
-// 16 waves x R rounds x (4096 / bpc) words = the 4096 words (16 KiB) the half fold image leaves:
-// 32 rounds at bpc 512, 64 at 1024, 128 at 2048
-constexpr uint32_t kStageMaxRounds(int bpc) { return uint32_t(bpc / 16); }
+// Lab bits of launch_wave3 alone, read where it picks the policy (the kernels ignore them): not words_policy's answer
+constexpr int kLabNoHold = 4;       // compute: Words::kPerRound everywhere (lab 95 / 163)
+constexpr int kLabNoStage = 1024;   // compute: Words::kHold8 / kPerRound where production stages the words (lab 122)
+constexpr int kLabStageWin = 2048;  // compute at bpc 512: staged past kStageMaxRounds too, window by window (lab 130)
 
 // Waves with at least this many rounds set their priority by the rounds they have left (round 3):
 // the SIMD arbiter favours older waves, so with equal work a workgroup's waves end staggered and its
@@ -224,18 +221,262 @@ struct SegWalk {
     }
 };
 
-// The core: prologue, steps, last step. VERIFY: compare with the stored words and fold the first bad
-// key into *result; else store the words. SOLO (overlapped verifies): the last step runs its two
-// rounds as single chains one after the other. HOLD (compute, bpc 512): the words of 8 rounds are
-// transposed into one VGPR and up to 8 such VGPRs are stored in one burst. LAB: lab-only bits (kLab*).
-template <int BPC, bool VERIFY, bool SOLO, bool HOLD, int LAB, int TPB, class Walk>
+// The stored words through a buffer resource on the round's (wave-uniform) word base: the lane's
+// offset is the only VGPR operand. A 64-bit VGPR address temporary may be allocated on registers
+// of a round still in flight, and the waitcnt pass then drains every load at the loop head.
+// Its range is the round's whole chunks: a partial round's stores past them are dropped.
+template <int BPC>
+__device__ inline __amdgpu_buffer_rsrc_t words_rsrc(const WView &v) {
+    return __builtin_amdgcn_make_buffer_rsrc(v.w, 0, __builtin_amdgcn_readfirstlane(v.nb / (BPC / 4)), 0x00020000);
+}
+
+// ---- a round's words: one unit per policy (Words, words_policy: launch_plan.h), three entries each, called by
+// all lanes of the wave:
+//   round(k, v, y, want)  round k (view v) has finished. y: its chunks' finished CRCs, byte-swapped (the affine
+//                         fold image carries init and final xor and the swap: y is the stored big-endian word
+//                         as it loads), in at least the first of each chunk's G lanes; want: the stored word
+//                         (kCompare; else 0). Rounds past the wave's last (k >= K) finish too and are dropped.
+//   step_end(kend)        after the step that finished round kend - 1
+//   wave_end()            after the wave's last step
+// LAB: the bits that alter a policy's inside (kLabStorePlain, kLabNoStore, kLabNearStore; verify: the wrong-CRC
+// diagnostics). step_end and wave_end are forced inline: left to the inliner, one wave_end stayed a call.
+template <Words W, int BPC, int LAB, class Walk>
+struct RoundWords;
+// What a unit sees of its wave, all by reference as a lambda's captures are: the walk, the policy's registers
+// (State, a local of wave_rounds), the verify's result word, the lane, its place j in its chunk, the wave's rounds
+template <class Walk, class State>
+struct WaveView {
+    Walk &walk;
+    State &st;
+    unsigned long long *result;  // verify
+    const uint32_t &lane, &j, &K;
+};
+struct NoFlush {
+    __device__ __forceinline__ void step_end(uint32_t) {}
+    __device__ __forceinline__ void wave_end() {}
+};
+
+// Verify: compare with the stored words and fold the first bad key into *result.
+template <int BPC, int LAB, class Walk>
+struct RoundWords<Words::kCompare, BPC, LAB, Walk> : NoFlush {
+    static constexpr int G = BPC / 64;
+    static constexpr bool kWrong = (LAB & (kLabNoMath | kLabNoFill | kLabNoTabLoad)) != 0;  // diagnostics: wrong CRCs
+    struct State {
+        uint32_t coff;  // the lane's chunk's first byte: the chunk is whole when coff < nb
+        __device__ __forceinline__ State(Walk &, uint32_t *, uint32_t lane) : coff((lane / G) * BPC) {}
+    };
+    WaveView<Walk, State> a;
+    __device__ void round(uint32_t k, const WView &v, uint32_t y, uint32_t want) {
+        if (k >= a.K || a.j != 0) return;
+        // the diagnostics compute wrong CRCs: compare inverted so they do not flag every chunk
+        // (an atomic per chunk would dominate their time); a partial round's lanes past its
+        // whole chunks computed zeros
+        if ((want != y) != kWrong && a.st.coff < v.nb)
+            __hip_atomic_fetch_max((gu64 *)a.result, ~(unsigned long long)(v.key + a.lane / G), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
+
+// Each round's words stored as the round finishes: the first lane of every chunk, one 4-byte store.
+template <int BPC, int LAB, class Walk>
+struct RoundWords<Words::kPerRound, BPC, LAB, Walk> : NoFlush {
+    static constexpr int G = BPC / 64;
+    struct State {
+        uint32_t woff;  // this lane's chunk word within a round
+        __device__ __forceinline__ State(Walk &, uint32_t *, uint32_t lane) : woff(4 * (lane / G)) {}
+    };
+    WaveView<Walk, State> a;
+    __device__ void round(uint32_t k, const WView &v, uint32_t y, uint32_t) {
+        if (k >= a.K || a.j != 0) return;
+        __builtin_amdgcn_raw_buffer_store_b32(y, words_rsrc<BPC>(v), a.st.woff, 0, 0);
+    }
+};
+
+// a held word's store. Round 4 measured these as system-scope nt stores too (the staged words'
+// policy): 1 GiB compute 160.6 -> 175.0 us at bpc 512 and 159.5 -> 182.6 at 4096
+// (profiles/r04/r4h_cmp_1g*): write-through 4-byte and 32-byte pieces cost what whole staged
+// lines do not, so they stay plain
+__device__ inline void held_store(gu8 *p, uint32_t v) { *(gu32 *)p = v; }
+
+// Compute at bpc 512: the words of 8 rounds are transposed into one VGPR and up to 8 such VGPRs are
+// stored in one burst. Lane 8r + c collects chunk c of round r of the current octet (8 rounds) in `line`;
+// up to 8 closed octets wait in hold[] (hold[i] = octet hold_base + nheld - 1 - i) and go out in one
+// burst. With a lane view their addresses come from the walk at flush time (one VGPR per held
+// octet); otherwise each lane keeps its word's address beside it (a segment walk's rounds may
+// belong to different segments).
+template <int BPC, int LAB, class Walk>
+struct RoundWords<Words::kHold8, BPC, LAB, Walk> : NoFlush {
+    static_assert(BPC == 512, "8 chunks per round");
+    static constexpr bool kAddr = !Walk::kLaneView;
+    struct State {
+        uint32_t line = 0;
+        uint32_t hold[8];
+        gu32 *laddr = nullptr;
+        gu32 *hold_addr[kAddr ? 8 : 1];
+        uint32_t nheld = 0, hold_base = 0;
+        __device__ __forceinline__ State(Walk &, uint32_t *, uint32_t) {}
+    };
+    WaveView<Walk, State> a;
+    __device__ void flush() {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            // kLabNoStore keeps the words live through a compare that practically never stores
+            if (uint32_t(i) < a.st.nheld && ((LAB & kLabNoStore) == 0 || a.st.hold[i] == 0x9E3779B9u)) {
+                if constexpr ((LAB & kLabNearStore) != 0 && !kAddr) {
+                    *(gu32 *)((gu8 *)a.walk.view(0).w + 4 * a.lane) = a.st.hold[i];
+                } else if constexpr (kAddr) {
+                    if (a.st.hold_addr[i]) *a.st.hold_addr[i] = a.st.hold[i];
+                } else {
+                    const uint32_t kk = 8 * (a.st.hold_base + a.st.nheld - 1 - i) + (a.lane >> 3);
+                    if (kk < a.K) {
+                        const WView v = a.walk.view(kk);
+                        if ((a.lane & 7) * BPC < v.nb) held_store((gu8 *)v.w + 4 * (a.lane & 7), a.st.hold[i]);
+                    }
+                }
+            }
+        }
+        a.st.hold_base += a.st.nheld;
+        a.st.nheld = 0;
+    }
+    __device__ void round(uint32_t k, const WView &v, uint32_t y, uint32_t) {
+        if (k >= a.K) return;
+        const uint32_t r = k & 7;
+        // group c's lanes all st.hold chunk c's state (group_xor is a butterfly)
+        const uint32_t got = uint32_t(__builtin_amdgcn_ds_bpermute(int(32 * (a.lane & 7)), int(y)));
+        const bool mine = (a.lane >> 3) == r;
+        a.st.line = mine ? got : a.st.line;
+        if constexpr (kAddr)
+            a.st.laddr = mine ? ((a.lane & 7) * BPC < v.nb ? (gu32 *)((gu8 *)v.w + 4 * (a.lane & 7)) : nullptr) : a.st.laddr;
+        if (r == 7 || k + 1 == a.K) {
+#pragma unroll
+            for (int i = 7; i > 0; --i) {
+                a.st.hold[i] = a.st.hold[i - 1];
+                if constexpr (kAddr) a.st.hold_addr[i] = a.st.hold_addr[i - 1];
+            }
+            a.st.hold[0] = a.st.line;
+            if constexpr (kAddr) {
+                a.st.hold_addr[0] = a.st.laddr;
+                a.st.laddr = nullptr;
+            }
+            if (++a.st.nheld == 8) flush();
+        }
+    }
+    __device__ __forceinline__ void wave_end() { flush(); }
+};
+
+// Compute at bpc 4096 (one word per round) over one contiguous block: lane k % 64 keeps round k's
+// word, and one store per 64 rounds writes them, instead of a 4-byte store per round into the read
+// stream: 128 MiB 23.63 -> 22.54 us overlapped, 25.24 -> 24.51 barriered, 1 GiB 160.6 -> 158.8
+// (verify 157.7; profiles/r03/reentry/r3zq_*)
+template <int BPC, int LAB, class Walk>
+struct RoundWords<Words::kHold64, BPC, LAB, Walk> : NoFlush {
+    static_assert(BPC == 4096 && Walk::kContiguous, "one word per round, a.lane-varying views");
+    struct State {
+        uint32_t line64 = 0;
+        __device__ __forceinline__ State(Walk &, uint32_t *, uint32_t) {}
+    };
+    WaveView<Walk, State> a;
+    __device__ void round(uint32_t k, const WView &, uint32_t y, uint32_t) {
+        // lane 0 holds the chunk's word (group_xor)
+        if (k >= a.K) return;
+        const uint32_t yy = __builtin_amdgcn_readfirstlane(y);
+        a.st.line64 = a.lane == (k & 63) ? yy : a.st.line64;
+        if ((k & 63) == 63 || k + 1 == a.K) {
+            const uint32_t kk = (k & ~63u) + a.lane;
+            if (a.lane <= (k & 63)) held_store((gu8 *)a.walk.view(kk).w, a.st.line64);
+        }
+    }
+};
+
+// Compute at bpc <= 2048 over a contiguous block, 1024-thread workgroups: every word of a window of
+// kStageMaxRounds rounds per wave waits in the LDS the half fold image leaves free (16 KiB: slot s's round k at
+// word (k * 16 + s) * CPW + c, CPW = 4096 / bpc words per round) and the workgroup writes them at its
+// end as whole runs of 16 * CPW words, since the 16 waves' k-th rounds are 16 consecutive units.
+// The held stores send each wave's words as 32-B pieces of lines that three other waves complete
+// later, into a saturated read stream: 0.4 us of the 1.1 us those writes cost an overlapped 128 MiB
+// launch (profiles/r03/reentry/r3zb_c128_*).
+// Past kSR rounds per wave (bpc 1024 / 2048; bpc 512 with lab 130) a window is written out
+// after the step that finishes round m * kSR - 1, for every m with m * kSR < kq (or m * kSR == kq when
+// some waves have kq + 1 rounds): every wave of the launch has at least kq rounds, so every wave runs
+// that step and meets both barriers. The last window goes out at the workgroup's end.
+template <int BPC, int LAB, class Walk>
+struct RoundWords<Words::kStaged, BPC, LAB, Walk> : NoFlush {
+    static_assert(BPC <= 2048 && Walk::kContiguous, "the half fold image; the 16 waves' rounds are consecutive units");
+    static constexpr int G = BPC / 64;
+    static constexpr uint32_t kCpw = 64 / G;                // chunk words per round
+    static constexpr uint32_t kSR = kStageMaxRounds(BPC);  // rounds per staging window
+    struct State {
+        uint32_t *stage;
+        uint32_t slot, kq_flush;  // flush at kend <= kq_flush
+        __device__ __forceinline__ State(Walk &w, uint32_t *lds, uint32_t)
+            : stage(lds + kLdsBytesWave / 4 - 4096), slot(threadIdx.x >> 6), kq_flush(w.kq - (w.kr == 0 ? 1u : 0u)) {}
+    };
+    WaveView<Walk, State> a;
+    // A staged word's store (round 4): system scope (sc0 sc1, written through the L2) and non-temporal
+    // (nt), through a buffer resource on the wave-uniform word base with the lane's byte offset as the
+    // only VGPR operand. The words then leave no dirty lines for the end-of-kernel release to write
+    // back. 128 MiB per launch, lab A/B against plain stores (lab 128) over two boxes: overlapped
+    // -0.64 / -0.29 us, barriered -0.86 us (profiles/r04/r4e_cmp_*, r4f_cmp_*); system scope alone
+    // -0.16 / -0.44 and -0.26, nt alone -0.22 / -0.21 and -0.14. The buffer offset is 31-bit:
+    // words_policy stages only launches whose words stay below 2 GiB (data below 256 GiB at bpc 512).
+    __device__ void stage_store(gu8 *p, uint32_t v) {
+        // kLabNoStore (diagnostic 118): the staged words are kept live (a store that practically never
+        // happens) but not written: what the flush's global stores cost a launch (wrong results)
+        if constexpr ((LAB & kLabNoStore) != 0) {
+            if (v != 0x9E3779B9u) return;
+        }
+        if constexpr ((LAB & kLabStorePlain) == 0) {
+            const uint64_t wb = rfl64(reinterpret_cast<uint64_t>(a.walk.words));
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                reinterpret_cast<void *>(wb), 0, 0x7FFFFFFF, 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b32(v, rs, uint32_t(reinterpret_cast<uint64_t>(p) - wb), 0, 1 | 2 | 16);
+        } else {
+            *(gu32 *)p = v;
+        }
+    }
+    __device__ void round(uint32_t k, const WView &, uint32_t y, uint32_t) {
+        if (k < a.K && a.j == 0) a.st.stage[((k % kSR) * 16 + a.st.slot) * kCpw + a.lane / G] = y;
+    }
+    __device__ __forceinline__ void step_end(uint32_t kend) {
+        if (kend % kSR == 0 && kend <= a.st.kq_flush && a.walk.kq != 0) {
+            lds_barrier();
+            const uint64_t wg_first = a.walk.first - a.st.slot;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const uint32_t t = threadIdx.x + 1024 * p, kk = t / (16 * kCpw), s = (t / kCpw) & 15, c = t % kCpw;
+                stage_store((gu8 *)a.walk.words + 4 * kCpw * (wg_first + s + uint64_t(kend - kSR + kk) * a.walk.stride) + 4 * c,
+                            a.st.stage[t]);
+            }
+            lds_barrier();
+        }
+    }
+    __device__ __forceinline__ void wave_end() {
+        lds_barrier();  // every wave of the workgroup runs wave_rounds to its end
+        const uint64_t wg_first = a.walk.first - a.st.slot;
+        const uint32_t wb = a.walk.kq ? kSR * (a.st.kq_flush / kSR) : 0u;  // the last window's first round
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const uint32_t t = threadIdx.x + 1024 * p, k = wb + t / (16 * kCpw), s = (t / kCpw) & 15, c = t % kCpw;
+            const uint32_t ks = a.walk.kq + (wg_first + s < a.walk.kr ? 1u : 0u);
+            if (k < ks)
+                stage_store((gu8 *)a.walk.words + 4 * (kRoundBytes / BPC) * (wg_first + s + uint64_t(k) * a.walk.stride) +
+                                4 * c,
+                            a.st.stage[t]);
+        }
+    }
+};
+
+// The core: fill, first loads, the loop of steps, the end. W: what becomes of a round's words (RoundWords;
+// Words::kCompare verifies). SOLO (overlapped launches): the last step runs its two rounds as single
+// chains one after the other. LAB: lab-only bits (kLab*).
+template <int BPC, bool SOLO, Words W, int LAB, int TPB, class Walk>
 __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uint32_t *__restrict__ g_tab,
                                             const uint32_t *__restrict__ g_nib, unsigned long long *result,
                                             unsigned long long *lab_mid = nullptr) {
     constexpr int G = BPC / 64;
     constexpr bool kHalfFold = G <= 32;
+    constexpr bool VERIFY = W == Words::kCompare;
     constexpr bool LATE = (LAB & kLabEarly) == 0, NOMATH = (LAB & kLabNoMath) != 0;
-    constexpr bool kWrong = (LAB & (kLabNoMath | kLabNoFill | kLabNoTabLoad)) != 0;  // diagnostics: wrong CRCs (verify)
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t j = lane % G;
     const uint32_t lane_off = 64 * (lane & 15) + 16 * (lane >> 4);
@@ -268,8 +509,8 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
     WView cv0 = walk.view(0), cv1 = walk.view(1);
     __builtin_amdgcn_sched_barrier(0);
     Round a0, a1, b0, b1;
-    load_round_buf<true>(a0, cv0.p, lane_off, cv0.nb);
-    load_round_buf<true>(a1, cv1.p, lane_off, cv1.nb);
+    load_round_buf(a0, cv0.p, lane_off, cv0.nb);
+    load_round_buf(a1, cv1.p, lane_off, cv1.nb);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int f = 0; f < kFillIters; ++f) {
@@ -299,175 +540,13 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
         return nf.apply(x);
     };
     const uint32_t woff = 4 * (lane / G);  // this lane's chunk word within a round
-    const uint32_t coff = (lane / G) * BPC;  // its chunk's first byte: the chunk is whole when coff < nb
+    typename RoundWords<W, BPC, LAB, Walk>::State st(walk, lds, lane);  // the policy's registers
+    RoundWords<W, BPC, LAB, Walk> out{{}, {walk, st, result, lane, j, K}};
     WView pv0 = walk.view(2), pv1 = walk.view(3);
 
-    // The stored words through a buffer resource on the round's (wave-uniform) word base: the lane's
-    // offset is the only VGPR operand. A 64-bit VGPR address temporary may be allocated on registers
-    // of a round still in flight, and the waitcnt pass then drains every load at the loop head.
-    // Its range is the round's whole chunks: a partial round's stores past them are dropped.
-    auto wrsrc = [](const WView &v) {
-        return __builtin_amdgcn_make_buffer_rsrc(v.w, 0, __builtin_amdgcn_readfirstlane(v.nb / (BPC / 4)), 0x00020000);
-    };
     auto want_of = [&](const WView &v) -> uint32_t {
-        if constexpr (VERIFY) return __builtin_amdgcn_raw_buffer_load_b32(wrsrc(v), woff, 0, 0);
+        if constexpr (VERIFY) return __builtin_amdgcn_raw_buffer_load_b32(words_rsrc<BPC>(v), woff, 0, 0);
         return 0;
-    };
-    constexpr bool kHold = HOLD && !VERIFY && G == 8;
-    constexpr bool kAddr = !Walk::kLaneView;
-    // kHold: lane 8r + c collects chunk c of round r of the current octet (8 rounds) in `line`; up to
-    // 8 closed octets wait in hold[] (hold[i] = octet hold_base + nheld - 1 - i) and go out in one
-    // burst. With a lane view their addresses come from the walk at flush time (one VGPR per held
-    // octet); otherwise each lane keeps its word's address beside it (a segment walk's rounds may
-    // belong to different segments).
-    // a held word's store. Round 4 measured these as system-scope nt stores too (the staged words'
-    // policy): 1 GiB compute 160.6 -> 175.0 us at bpc 512 and 159.5 -> 182.6 at 4096
-    // (profiles/r04/r4h_cmp_1g*): write-through 4-byte and 32-byte pieces cost what whole staged
-    // lines do not, so they stay plain
-    auto held_store = [&](gu8 *p, uint32_t v) { *(gu32 *)p = v; };
-    uint32_t line = 0;
-    uint32_t hold[kHold ? 8 : 1];
-    gu32 *laddr = nullptr;
-    gu32 *hold_addr[kHold && kAddr ? 8 : 1];
-    uint32_t nheld = 0, hold_base = 0;
-    auto flush = [&]() {
-#pragma unroll
-        for (int i = 0; i < (kHold ? 8 : 0); ++i) {
-            // kLabNoStore keeps the words live through a compare that practically never stores
-            if (uint32_t(i) < nheld && ((LAB & kLabNoStore) == 0 || hold[i] == 0x9E3779B9u)) {
-                if constexpr ((LAB & kLabNearStore) != 0 && !kAddr) {
-                    *(gu32 *)((gu8 *)walk.view(0).w + 4 * lane) = hold[i];
-                } else if constexpr (kAddr) {
-                    if (hold_addr[i]) *hold_addr[i] = hold[i];
-                } else {
-                    const uint32_t kk = 8 * (hold_base + nheld - 1 - i) + (lane >> 3);
-                    if (kk < K) {
-                        const WView v = walk.view(kk);
-                        if ((lane & 7) * BPC < v.nb) held_store((gu8 *)v.w + 4 * (lane & 7), hold[i]);
-                    }
-                }
-            }
-        }
-        hold_base += nheld;
-        nheld = 0;
-    };
-    // y: the chunk's finished CRC, byte-swapped (the affine fold image carries init and final xor
-    // and the swap: y is the stored big-endian word as it loads)
-    // kStageWords (compute at bpc <= 2048 over a contiguous block): every word of a window of
-    // kStageMaxRounds rounds per wave waits in the LDS the half fold image leaves free (16 KiB: slot s's round k at
-    // word (k * 16 + s) * CPW + c, CPW = 4096 / bpc words per round) and the workgroup writes them at its
-    // end as whole runs of 16 * CPW words, since the 16 waves' k-th rounds are 16 consecutive units.
-    // The held stores send each wave's words as 32-B pieces of lines that three other waves complete
-    // later, into a saturated read stream: 0.4 us of the 1.1 us those writes cost an overlapped 128 MiB
-    // launch (profiles/r03/reentry/r3zb_c128_*).
-    constexpr bool kStage = !VERIFY && (LAB & kStageWords) != 0 && Walk::kContiguous && kHalfFold && TPB == 1024;
-    constexpr uint32_t kCpw = 64 / G;  // chunk words per round
-    constexpr uint32_t kSR = kStageMaxRounds(BPC);  // rounds per staging window
-    uint32_t *stage = lds + kLdsBytesWave / 4 - 4096;
-    const uint32_t slot = threadIdx.x >> 6;
-    // Past kSR rounds per wave (bpc 1024 / 2048; bpc 512 with kLabStageWin) a window is written out
-    // after the step that finishes round m * kSR - 1, for every m with m * kSR < kq (or m * kSR == kq when
-    // some waves have kq + 1 rounds): every wave of the launch has at least kq rounds, so every wave runs
-    // that step and meets both barriers. The last window goes out at the workgroup's end.
-    // A staged word's store (round 4): system scope (sc0 sc1, written through the L2) and non-temporal
-    // (nt), through a buffer resource on the wave-uniform word base with the lane's byte offset as the
-    // only VGPR operand. The words then leave no dirty lines for the end-of-kernel release to write
-    // back. 128 MiB per launch, lab A/B against plain stores (lab 128) over two boxes: overlapped
-    // -0.64 / -0.29 us, barriered -0.86 us (profiles/r04/r4e_cmp_*, r4f_cmp_*); system scope alone
-    // -0.16 / -0.44 and -0.26, nt alone -0.22 / -0.21 and -0.14. The buffer offset is 31-bit:
-    // launch_wave3 stages only launches whose words stay below 2 GiB (data below 256 GiB at bpc 512).
-    auto stage_store = [&](gu8 *p, uint32_t v) {
-        // kLabNoStore (diagnostic 118): the staged words are kept live (a store that practically never
-        // happens) but not written: what the flush's global stores cost a launch (wrong results)
-        if constexpr ((LAB & kLabNoStore) != 0) {
-            if (v != 0x9E3779B9u) return;
-        }
-        if constexpr (kStage && (LAB & kLabStorePlain) == 0) {
-            const uint64_t wb = rfl64(reinterpret_cast<uint64_t>(walk.words));
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                reinterpret_cast<void *>(wb), 0, 0x7FFFFFFF, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b32(v, rs, uint32_t(reinterpret_cast<uint64_t>(p) - wb), 0, 1 | 2 | 16);
-        } else {
-            *(gu32 *)p = v;
-        }
-    };
-    uint32_t kq_flush = 0;  // flush at kend <= kq_flush
-    if constexpr (kStage) kq_flush = walk.kq - (walk.kr == 0 ? 1u : 0u);
-    auto stage_flush = [&](uint32_t kend) {
-        if constexpr (kStage) {
-            if (kend % kSR == 0 && kend <= kq_flush && walk.kq != 0) {
-                lds_barrier();
-                const uint64_t wg_first = walk.first - slot;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const uint32_t t = threadIdx.x + 1024 * p, kk = t / (16 * kCpw), s = (t / kCpw) & 15,
-                                   c = t % kCpw;
-                    stage_store((gu8 *)walk.words +
-                                    4 * kCpw * (wg_first + s + uint64_t(kend - kSR + kk) * walk.stride) + 4 * c,
-                                stage[t]);
-                }
-                lds_barrier();
-            }
-        }
-    };
-    // compute at bpc 4096 (one word per round) over one contiguous block: lane k % 64 keeps round k's
-    // word, and one store per 64 rounds writes them, instead of a 4-byte store per round into the read
-    // stream: 128 MiB 23.63 -> 22.54 us overlapped, 25.24 -> 24.51 barriered, 1 GiB 160.6 -> 158.8
-    // (verify 157.7; profiles/r03/reentry/r3zq_*)
-    constexpr bool kHold64 = !VERIFY && G == 64 && Walk::kContiguous && (LAB & kLabNoHold) == 0;
-    uint32_t line64 = 0;
-    auto finish = [&](uint32_t k, const WView &v, uint32_t y, uint32_t want) {
-        if constexpr (kHold64) {
-            // lane 0 holds the chunk's word (group_xor)
-            if (k >= K) return;
-            const uint32_t yy = __builtin_amdgcn_readfirstlane(y);
-            line64 = lane == (k & 63) ? yy : line64;
-            if ((k & 63) == 63 || k + 1 == K) {
-                const uint32_t kk = (k & ~63u) + lane;
-                if (lane <= (k & 63)) held_store((gu8 *)walk.view(kk).w, line64);
-            }
-            return;
-        }
-        if constexpr (kStage) {
-            if (k < K && j == 0) stage[((k % kSR) * 16 + slot) * kCpw + lane / G] = y;
-            return;
-        }
-        if constexpr (kHold) {
-            if (k >= K) return;
-            const uint32_t r = k & 7;
-            // group c's lanes all hold chunk c's state (group_xor is a butterfly)
-            const uint32_t got = uint32_t(__builtin_amdgcn_ds_bpermute(int(32 * (lane & 7)), int(y)));
-            const bool mine = (lane >> 3) == r;
-            line = mine ? got : line;
-            if constexpr (kAddr)
-                laddr = mine ? ((lane & 7) * BPC < v.nb ? (gu32 *)((gu8 *)v.w + 4 * (lane & 7)) : nullptr) : laddr;
-            if (r == 7 || k + 1 == K) {
-#pragma unroll
-                for (int i = (kHold ? 7 : 0); i > 0; --i) {
-                    hold[i] = hold[i - 1];
-                    if constexpr (kAddr) hold_addr[i] = hold_addr[i - 1];
-                }
-                hold[0] = line;
-                if constexpr (kAddr) {
-                    hold_addr[0] = laddr;
-                    laddr = nullptr;
-                }
-                if (++nheld == 8) flush();
-            }
-            return;
-        }
-        if (k >= K || j != 0) return;
-        const uint32_t c = y;
-        if constexpr (VERIFY) {
-            // the diagnostics compute wrong CRCs: compare inverted so they do not flag every chunk
-            // (an atomic per chunk would dominate their time); a partial round's lanes past its
-            // whole chunks computed zeros
-            if ((want != c) != kWrong && coff < v.nb)
-                __hip_atomic_fetch_max((gu64 *)result, ~(unsigned long long)(v.key + lane / G), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b32(c, wrsrc(v), woff, 0, 0);
-        }
     };
     auto word = [](const Round &r, int i) -> uint32_t { return r.w[i >> 2][i & 3]; };
     // the table step of one word (kLabNoMath, diagnostic: a plain XOR instead, wrong on purpose)
@@ -483,20 +562,6 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
         x1 = word(c1, 0);
         Look l0 = look(x0), l1;
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr ((LAB & kLabFull16) != 0) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                l1 = look(x1);
-                __builtin_amdgcn_sched_barrier(0);
-                x0 = combine(l0, i < 15 ? word(c0, i < 15 ? i + 1 : 15) : 0u);
-                __builtin_amdgcn_sched_barrier(0);
-                if (i < 15) l0 = look(x0);
-                __builtin_amdgcn_sched_barrier(0);
-                x1 = combine(l1, i < 15 ? word(c1, i < 15 ? i + 1 : 15) : 0u);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            return;
-        }
 #pragma unroll
         for (int i = 0; i < 15; ++i) {
             l1 = look(x1);
@@ -513,14 +578,9 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
     // identical code otherwise gets tail-merged into one copy that both run (register copies in).
     auto solo = [&](Round &c, const WView &v, uint32_t k, uint32_t w, auto id) {
         uint32_t x = word(c, 0);
-        if constexpr ((LAB & kLabFull16) != 0) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) x = combine(look(x), i < 15 ? word(c, i < 15 ? i + 1 : 15) : 0u);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 15; ++i) x = combine(look(x), word(c, i + 1));
-        }
-        finish(k, v, group_xor<G>(fold(x)), w);
+        for (int i = 0; i < 15; ++i) x = combine(look(x), word(c, i + 1));
+        out.round(k, v, group_xor<G>(fold(x)), w);
         if constexpr (decltype(id)::value == 0) asm volatile("; solo round 0" ::: "memory");
         else asm volatile("; solo round 1" ::: "memory");
     };
@@ -546,8 +606,8 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
         prio(k);
         const uint32_t w0 = want_of(cv0), w1 = want_of(cv1);
         if constexpr (!LATE) {
-            load_round_buf<true>(p0, pv0.p, lane_off, pv0.nb);
-            load_round_buf<true>(p1, pv1.p, lane_off, pv1.nb);
+            load_round_buf(p0, pv0.p, lane_off, pv0.nb);
+            load_round_buf(p1, pv1.p, lane_off, pv1.nb);
         }
         __builtin_amdgcn_sched_barrier(0);
         regroup(c0);
@@ -557,15 +617,15 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
         }
         if constexpr (LATE) {
             __builtin_amdgcn_sched_barrier(0);
-            load_round_buf<true>(p0, pv0.p, lane_off, pv0.nb);
-            load_round_buf<true>(p1, pv1.p, lane_off, pv1.nb);
+            load_round_buf(p0, pv0.p, lane_off, pv0.nb);
+            load_round_buf(p1, pv1.p, lane_off, pv1.nb);
             __builtin_amdgcn_sched_barrier(0);
         }
         uint32_t x0, x1;
         chains(c0, c1, x0, x1);
-        finish(k, cv0, group_xor<G>(fold(x0)), w0);
-        finish(k + 1, cv1, group_xor<G>(fold(x1)), w1);
-        stage_flush(k + 2);
+        out.round(k, cv0, group_xor<G>(fold(x0)), w0);
+        out.round(k + 1, cv1, group_xor<G>(fold(x1)), w1);
+        out.step_end(k + 2);
         __builtin_amdgcn_sched_barrier(0);
         cv0 = pv0;
         cv1 = pv1;
@@ -591,7 +651,7 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
             solo(c0, cv0, k, w0, std::integral_constant<int, 0>{});
             regroup(c1);
             solo(c1, cv1, k + 1, w1, std::integral_constant<int, 1>{});
-            stage_flush(k + 2);
+            out.step_end(k + 2);
         };
         if (nr != 0) {
             const uint32_t kl = nr - 2;  // the last step's first round
@@ -617,22 +677,7 @@ __device__ __forceinline__ void wave_rounds(Walk &walk, uint32_t *lds, const uin
             step(b0, b1, a0, a1, k + 2);
         }
     }
-    if constexpr (kStage) {
-        lds_barrier();  // every wave of the workgroup runs wave_rounds to its end
-        const uint64_t wg_first = walk.first - slot;
-        const uint32_t wb = walk.kq ? kSR * (kq_flush / kSR) : 0u;  // the last window's first round
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint32_t t = threadIdx.x + 1024 * p, k = wb + t / (16 * kCpw), s = (t / kCpw) & 15, c = t % kCpw;
-            const uint32_t ks = walk.kq + (wg_first + s < walk.kr ? 1u : 0u);
-            if (k < ks)
-                stage_store((gu8 *)walk.words + 4 * (kRoundBytes / BPC) * (wg_first + s + uint64_t(k) * walk.stride) +
-                                4 * c,
-                            stage[t]);
-        }
-    } else if constexpr (kHold) {
-        flush();
-    }
+    out.wave_end();
 }
 
 // Slow region of one contiguous run: the chunks after its last whole round plus its short tail, one
@@ -678,11 +723,12 @@ __device__ __forceinline__ void short_tail(const uint32_t *lds, const uint8_t *s
     }
 }
 
-// One block (PITCH = false) or a constant-pitch stream (PITCH = true, ChunkLaunch::pitch/npk/geom).
-template <int BPC, bool VERIFY, bool PITCH, bool SOLO, int LAB = 0, int TPB = kBlockThreads>
+// One block (PITCH = false) or a constant-pitch stream (PITCH = true, ChunkLaunch::pitch/npk/geom); W: its word policy
+template <int BPC, bool VERIFY, bool PITCH, bool SOLO, Words W, int LAB = 0, int TPB = kBlockThreads>
 __global__ __launch_bounds__(TPB) void crc32c_wave_kernel(ChunkLaunch a, const uint32_t *__restrict__ g_tab,
                                                                     const uint32_t *__restrict__ g_nib) {
     static_assert(BPC <= kRoundBytes && BPC % 512 == 0, "one-round units");
+    static_assert(VERIFY == (W == Words::kCompare) && (W != Words::kStaged || TPB == 1024), "words_policy's answers");
     __shared__ __attribute__((aligned(16))) uint32_t lds[kLdsBytesWave / 4];
     constexpr int kCpu = kRoundBytes / BPC;
     constexpr int kWpb = TPB / 64;
@@ -690,7 +736,6 @@ __global__ __launch_bounds__(TPB) void crc32c_wave_kernel(ChunkLaunch a, const u
     const uint64_t wave = uint64_t(blockIdx.x) * kWpb + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint8_t *words = VERIFY ? const_cast<uint8_t *>(a.crc_be) : a.out_be;
     const uint8_t *dummy = reinterpret_cast<const uint8_t *>(g_tab);
-    constexpr bool kHold = !VERIFY && BPC == 512 && (LAB & kLabNoHold) == 0;
     // the wave's round count from the host's split (ChunkLaunch::kq/kr): SALU only
     const uint32_t K = a.kq + (wave < a.kr ? 1u : 0u);
     unsigned long long lab_mid[3] = {0, 0, 0};  // kLabMid only
@@ -706,14 +751,14 @@ __global__ __launch_bounds__(TPB) void crc32c_wave_kernel(ChunkLaunch a, const u
         const PacketGeom &g = a.geom;
         PitchWalk<kCpu> w{a.data, words, a.pitch, a.crc_pitch ? a.crc_pitch : a.pitch, wave, nwaves, K,
                           g.upp, g.magic, g.shift, g.ptail, g.lunits, g.ltail, uint32_t(a.npk - 1), dummy};
-        wave_rounds<BPC, VERIFY, SOLO, kHold, LAB, TPB>(w, lds, g_tab, g_nib, a.result);
+        wave_rounds<BPC, SOLO, W, LAB, TPB>(w, lds, g_tab, g_nib, a.result);
         const uint64_t lp = a.npk - 1;
         if (a.last_len % BPC)  // wave-uniform: only the last packet's short chunk is left
             short_tail<BPC, VERIFY, TPB>(lds, a.data + lp * a.pitch, words + lp * w.wpitch, a.last_len, lp << 32,
                                          a.check_short_tail, a.result);
     } else {
         BlockWalk<kCpu> w{a.data, words, a.chunk_base, wave, nwaves, K, dummy, a.kq, a.kr};
-        wave_rounds<BPC, VERIFY, SOLO, kHold, LAB, TPB>(w, lds, g_tab, g_nib, a.result, lab_mid);
+        wave_rounds<BPC, SOLO, W, LAB, TPB>(w, lds, g_tab, g_nib, a.result, lab_mid);
         if (a.len % kRoundBytes)  // wave-uniform: a block of whole rounds has no slow region
             slow_region<BPC, VERIFY, TPB>(lds, a.data, words, a.len, a.chunk_base, a.check_short_tail, a.result);
     }
@@ -742,7 +787,8 @@ __global__ __launch_bounds__(TPB) void crc32c_segments_kernel(SegLaunch L, const
     const uint64_t wave = uint64_t(blockIdx.x) * kWpb + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     SegWalk<kCpu, UNI> w{(CSegLaunch *)(&L), wave, nwaves, L.kq + (wave < L.kr ? 1u : 0u),
                          reinterpret_cast<const uint8_t *>(g_tab)};
-    wave_rounds<BPC, VERIFY, false, !VERIFY && BPC == 512, LAB, TPB>(w, lds, g_tab, g_nib, L.result);
+    constexpr Words kWords = words_policy(VERIFY, WalkKind::kSeg, BPC, TPB, kAnyUnits, 0, 0);  // whatever its size
+    wave_rounds<BPC, false, kWords, LAB, TPB>(w, lds, g_tab, g_nib, L.result);
 
     // every whole chunk was in a (possibly partial) round: only the segments' short last chunks
     // are left, one lane each, item i on workgroup i % grid (piece CRCs for a combine: the caller's)
@@ -781,12 +827,13 @@ __global__ __launch_bounds__(TPB) void crc32c_segments_kernel(SegLaunch L, const
 // barriered and +1 % at 1 GiB with it).
 constexpr uint64_t kSoloTailMaxBytes = uint64_t(256) << 20;
 
-// SOLO: the solo last step when the launch qualifies (above); LAB: lab A/B bits.
-template <int BPC, bool V, bool PITCH, bool SOLO, int LAB = 0, int TPB = kBlockThreads>
+// SOLO: the solo last step when the launch qualifies (above); LAB: lab A/B bits. SMALL: a launch known to
+// have at most 4096 units (the 256-thread workgroups below), for which words_policy's answer is a constant.
+template <int BPC, bool V, bool PITCH, bool SOLO, int LAB = 0, int TPB = kBlockThreads, bool SMALL = false>
 hipError_t launch_wave3(const ChunkLaunch &a, const uint32_t *tab, const uint32_t *fold, int grid_cap, hipStream_t s) {
     constexpr int G = BPC / 64;
     constexpr int set = G == 8 ? 0 : G == 16 ? 1 : G == 32 ? 2 : 3;
-    const uint32_t *nib = fold + ((LAB & kLabFull16) ? kFoldAffineOldOff : kFoldAffineOff) + set * kFoldNibbleWords;
+    const uint32_t *nib = fold + kFoldAffineOff + set * kFoldNibbleWords;
     const uint64_t units = PITCH ? (a.npk - 1) * a.geom.upp + a.geom.lunits : a.len / kRoundBytes;
     const uint64_t rpw = (LAB & kLabOneRound) != 0 && units <= 4096 ? 1 : 2;  // rounds per wave planned
     const uint64_t need = (units + rpw * (TPB / 64) - 1) / (rpw * (TPB / 64));
@@ -808,39 +855,42 @@ hipError_t launch_wave3(const ChunkLaunch &a, const uint32_t *tab, const uint32_
     // 10.16 -> 9.04 / 8.82 -> 8.53; 64 MiB 14.57 -> 13.90 / 13.36 -> 12.56; the block reader's
     // 64-packet batch (4 MiB, cache-resident) 7.00 -> 4.43. 128 MiB stays at 1024 (256 / 512 threads:
     // +6.1 / +0.4 us barriered). Compute over a contiguous block keeps 1024 threads: its staged words
-    // need the whole LDS; compute over a packet stream (the writer's batches: held stores) does not.
+    // need the whole LDS; compute over a packet stream (the writer's batches) does not.
     if constexpr ((V || PITCH) && TPB == 1024 && (LAB & kLabWg1024) == 0) {
-        // compute over a packet stream of <= 16 MiB (the writer's batches): each round's words stored at
-        // once. With two rounds per wave the held stores only delay the words to the wave's end: the
-        // writer's 64-packet batch 5.32 -> 4.47 us against 4.41 for its verify (lab 163, round 6,
-        // profiles/r06/r6n_partial_rate.jsonl)
-        constexpr int kSmall = (!V && PITCH) ? kLabNoHold : 0;
-        if (units <= 4096) return launch_wave3<BPC, V, PITCH, SOLO, LAB | kSmall, 256>(a, tab, fold, grid_cap, s);
+        if (units <= 4096) return launch_wave3<BPC, V, PITCH, SOLO, LAB, 256, true>(a, tab, fold, grid_cap, s);
         if (units <= 16384) return launch_wave3<BPC, V, PITCH, SOLO, LAB, 512>(a, tab, fold, grid_cap, s);
     }
-    // compute at bpc <= 2048 over one contiguous block: staged words; at bpc 512 only while they fit one
-    // window (beyond it the held stores measured faster at 1 GiB: 160.4 against 163.1 us in windows)
-    if constexpr (!V && BPC <= 2048 && !PITCH && TPB == 1024 &&
-                  (LAB & (kStageWords | kLabNoStage | kLabNoHold)) == 0) {
-        const bool words_fit = units * uint64_t(4 * (kRoundBytes / BPC)) < (uint64_t(1) << 31);  // stage_store
-        if (words_fit && (b.kq + (b.kr ? 1u : 0u) <= kStageMaxRounds(BPC) || BPC != 512 || (LAB & kLabStageWin) != 0))
-            return launch_wave3<BPC, V, PITCH, SOLO, LAB | kStageWords, TPB>(a, tab, fold, grid_cap, s);
-    }
-    if (a.overlap_previous) {  // AQL packet without the barrier bit (HDFS3_LAUNCH_OVERLAP_PREVIOUS)
-        if constexpr (SOLO) {
-            if (units * kRoundBytes <= kSoloTailMaxBytes) {
-                hipExtLaunchKernelGGL((crc32c_wave_kernel<BPC, V, PITCH, true, LAB, TPB>), dim3(grid),
-                                      dim3(TPB), 0, s, nullptr, nullptr, hipExtAnyOrderLaunch, b, tab, nib);
-                return hipGetLastError();
+    // the launch with word policy w; overlapped ones with the solo last step when SOLO and small enough (above)
+    auto go = [&](auto w) {
+        constexpr Words W = decltype(w)::value;
+        if (a.overlap_previous) {  // AQL packet without the barrier bit (HDFS3_LAUNCH_OVERLAP_PREVIOUS)
+            if constexpr (SOLO) {
+                if (units * kRoundBytes <= kSoloTailMaxBytes) {
+                    hipExtLaunchKernelGGL((crc32c_wave_kernel<BPC, V, PITCH, true, W, LAB, TPB>), dim3(grid),
+                                          dim3(TPB), 0, s, nullptr, nullptr, hipExtAnyOrderLaunch, b, tab, nib);
+                    return hipGetLastError();
+                }
             }
+            hipExtLaunchKernelGGL((crc32c_wave_kernel<BPC, V, PITCH, false, W, LAB, TPB>), dim3(grid),
+                                  dim3(TPB), 0, s, nullptr, nullptr, hipExtAnyOrderLaunch, b, tab, nib);
+        } else {
+            hipLaunchKernelGGL((crc32c_wave_kernel<BPC, V, PITCH, false, W, LAB, TPB>), dim3(grid), dim3(TPB),
+                               0, s, b, tab, nib);
         }
-        hipExtLaunchKernelGGL((crc32c_wave_kernel<BPC, V, PITCH, false, LAB, TPB>), dim3(grid),
-                              dim3(TPB), 0, s, nullptr, nullptr, hipExtAnyOrderLaunch, b, tab, nib);
-    } else {
-        hipLaunchKernelGGL((crc32c_wave_kernel<BPC, V, PITCH, false, LAB, TPB>), dim3(grid), dim3(TPB),
-                           0, s, b, tab, nib);
+        return hipGetLastError();
+    };
+    // The policy is words_policy's answer for this launch: kStaged while its words fit, else what a launch of
+    // no known size gets (SMALL: one of 4096 units), so at most these two kernels are built. The lab's other
+    // choices are made here: 95 / 163 store per round, 122 does not stage, 130 stages as if in one window.
+    constexpr WalkKind kWalk = PITCH ? WalkKind::kPitch : WalkKind::kBlock;
+    constexpr bool kPerRoundLab = !V && (LAB & kLabNoHold) != 0, kNoStageLab = (LAB & kLabNoStage) != 0;
+    if constexpr (!kPerRoundLab && !kNoStageLab && words_policy(V, kWalk, BPC, TPB, 1, 1, 0) == Words::kStaged) {
+        const bool win = (LAB & kLabStageWin) != 0;
+        if (words_policy(V, kWalk, BPC, TPB, units, win ? 0 : b.kq, win ? 0 : b.kr) == Words::kStaged)
+            return go(std::integral_constant<Words, Words::kStaged>());
     }
-    return hipGetLastError();
+    constexpr Words kElse = words_policy(V, kWalk, BPC, TPB, SMALL ? 4096 : kAnyUnits, ~0u, 0);
+    return go(std::integral_constant<Words, kPerRoundLab ? Words::kPerRound : kElse>());
 }
 
 // The grid and the waves' round split (SegLaunch::kq/kr) are set here. Small launches take
@@ -856,7 +906,7 @@ hipError_t launch_segments3(const SegLaunch &in, const uint32_t *tab, const uint
     constexpr int G = BPC / 64;
     constexpr int set = G == 8 ? 0 : G == 16 ? 1 : G == 32 ? 2 : 3;
     constexpr uint64_t kWpb = TPB / 64;
-    const uint32_t *nib = fold + ((LAB & kLabFull16) ? kFoldAffineOldOff : kFoldAffineOff) + set * kFoldNibbleWords;
+    const uint32_t *nib = fold + kFoldAffineOff + set * kFoldNibbleWords;
     SegLaunch L = in;
     const uint64_t need = (L.units + 2 * kWpb - 1) / (2 * kWpb);
     const uint64_t tail_need = (L.nseg + TPB - 1) / TPB;

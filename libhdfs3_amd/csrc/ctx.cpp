@@ -42,12 +42,7 @@ int hip_fail(hipError_t e, const char *what) {
 // Per polynomial ([0] CRC32C, [1] CRC32): slice tables, then the fold image (kFoldWords
 // matrix columns, then the 4 affine nibble-table sets for G = 8, 16, 32, 64 of the round
 // kernel), built once per process.
-// the device copy: the product stops before the lab-only sets
-#if HDFS3_LAB
-constexpr size_t kFoldUploadBytes = sizeof(uint32_t) * kFoldImageWords;
-#else
-constexpr size_t kFoldUploadBytes = sizeof(uint32_t) * kFoldAffineOldOff;
-#endif
+constexpr size_t kFoldUploadBytes = sizeof(uint32_t) * kFoldImageWords;  // the device copy
 
 struct HostImage {
     uint32_t t[kSlices][kTableEntries];
@@ -66,11 +61,6 @@ const HostImage *host_images() {
                 uint32_t *nib = img[p].fold + kFoldAffineOff + set * kFoldNibbleWords;
                 build_fold_nibbles_pre(img[p].t[0], img[p].fold, set, nib);
                 build_fold_affine(img[p].t[0], set, nib);
-#if HDFS3_LAB  // the round-4 sets of lab variant 157; the product never reads them (nor uploads them)
-                uint32_t *old = img[p].fold + kFoldAffineOldOff + set * kFoldNibbleWords;
-                build_fold_nibbles(img[p].fold, set, old);
-                build_fold_affine(img[p].t[0], set, old);
-#endif
             }
         }
     });

@@ -23,6 +23,41 @@ constexpr bool round_bpc(uint32_t bpc) { return bpc == 512 || bpc == 1024 || bpc
 // chunks of R >= 2 whole rounds: 4096-byte piece CRCs + a combine
 constexpr bool pieces_bpc(uint32_t bpc) { return bpc > uint32_t(kRoundBytes) && bpc % kRoundBytes == 0; }
 
+// ---- the round kernel's word output (crc32c_wave.h: RoundWords) -----------------------------------
+// What becomes of the CRC words a round finishes; each policy's code and measurements are one RoundWords unit.
+enum class Words {
+    kCompare,   // verify
+    kPerRound,  // each round's words stored as the round finishes
+    kHold8,     // bpc 512: 8 rounds' words per VGPR, up to 8 such VGPRs stored in one burst
+    kHold64,    // bpc 4096: 64 rounds' words in one VGPR, one store per 64 rounds
+    kStaged,    // a window of rounds staged in LDS, written by the workgroup as whole lines
+};
+enum class WalkKind { kBlock, kPitch, kSeg };  // BlockWalk, PitchWalk, SegWalk (crc32c_wave.h)
+// 16 waves x R rounds x (4096 / bpc) words = the 4096 words (16 KiB) the half fold image leaves:
+// 32 rounds at bpc 512, 64 at 1024, 128 at 2048
+constexpr uint32_t kStageMaxRounds(int bpc) { return uint32_t(bpc / 16); }
+constexpr uint64_t kAnyUnits = ~uint64_t(0);  // words_policy: a launch of no known size
+// The policy of one launch of the round kernel: `units` rounds over workgroups of `tpb` threads, every wave
+// kq rounds and the first kr waves one more (ChunkLaunch::kq/kr). The only place that decides it.
+constexpr Words words_policy(bool verify, WalkKind walk, int bpc, int tpb, uint64_t units, uint32_t kq, uint32_t kr) {
+    if (verify) return Words::kCompare;
+    if (walk == WalkKind::kBlock) {
+        if (bpc == 4096) return Words::kHold64;
+        // staged words need the whole LDS of a 1024-thread workgroup and a 31-bit store offset (words below
+        // 2 GiB); at bpc 512 only while they fit one window (beyond it the held stores measured faster at
+        // 1 GiB: 160.4 against 163.1 us in windows)
+        const bool fit = tpb == 1024 && units * uint64_t(4 * (kRoundBytes / bpc)) < (uint64_t(1) << 31);
+        if (fit && (bpc != 512 || uint64_t(kq) + (kr ? 1u : 0u) <= kStageMaxRounds(512))) return Words::kStaged;
+        return bpc == 512 ? Words::kHold8 : Words::kPerRound;
+    }
+    // compute over a packet stream of <= 16 MiB (the writer's batches, 256-thread workgroups): each round's
+    // words stored at once. With two rounds per wave the held stores only delay the words to the wave's end:
+    // the writer's 64-packet batch 5.32 -> 4.47 us against 4.41 for its verify (lab 163, round 6,
+    // profiles/r06/r6n_partial_rate.jsonl)
+    if (walk == WalkKind::kPitch && units <= 4096) return Words::kPerRound;
+    return bpc == 512 ? Words::kHold8 : Words::kPerRound;  // a segment walk holds with per-lane addresses
+}
+
 // The 4 KiB units of a packet stream (PitchWalk, crc32c_wave.h). A packet of whole chunks is
 // ceil(bytes / 4096) units; its last unit may be PARTIAL (the writer's 127-chunk packets at bpc
 // 512: 65,024 B = 15 whole rounds + 3,584 B, OutputStreamImpl.cpp:161-170): its loads are bounded by

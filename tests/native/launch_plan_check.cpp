@@ -1,7 +1,8 @@
 // CPU check of the launch planner (libhdfs3_amd/csrc/launch_plan.cpp), built with the host compiler
-// under ASan + UBSan by tests/test_launch_plan.py. Three parts: the unit -> packet multiply-shift of
+// under ASan + UBSan by tests/test_launch_plan.py. Four parts: the unit -> packet multiply-shift of
 // PacketGeom, the pitch walk's coverage of a stream's bytes (a host model of PitchWalk::view,
-// crc32c_wave.h), and the route plan_packet_batch picks for small descriptor lists. The expected
+// crc32c_wave.h), the route plan_packet_batch picks for small descriptor lists, and the word policy
+// words_policy gives a launch of the round kernel. The expected
 // routes are read off the branch conditions of launch_packet_batch as it stood before the planner
 // was split out of it ("before:" = that function's line in crc32c_kernels.hip at commit 023ec6b).
 #include <cstdio>
@@ -280,12 +281,84 @@ void check_routes() {
     CHECK(!plan_packet_stream(65536, 100, 1, 512, data, words, 0, true, 0, &s), "one packet without a whole chunk");
 }
 
+// ---- d. the round kernel's word policy ------------------------------------------------------------
+// words_policy against the table of launches it has to reproduce (what launch_wave3 and the two kernels
+// chose before the rule was written once), with the edges of its three run-time conditions
+void check_words() {
+    using W = Words;
+    using K = WalkKind;
+    constexpr uint64_t kGiB2 = uint64_t(1) << 31;
+    struct Row {
+        bool verify;
+        K walk;
+        int bpc, tpb;
+        uint64_t units;
+        uint32_t kq, kr;
+        W want;
+    };
+    const Row rows[] = {
+        // verify compares, whatever the walk, chunk size and launch size
+        {true, K::kBlock, 512, 256, 8, 2, 0, W::kCompare},
+        {true, K::kBlock, 4096, 1024, 1 << 20, 256, 0, W::kCompare},
+        {true, K::kPitch, 1024, 512, 8192, 8, 0, W::kCompare},
+        {true, K::kSeg, 512, 1024, 100000, 24, 1696, W::kCompare},
+        // compute over a contiguous block
+        {false, K::kBlock, 4096, 1024, 32768, 8, 0, W::kHold64},
+        {false, K::kBlock, 4096, 1024, 1, 0, 1, W::kHold64},
+        {false, K::kBlock, 1024, 1024, 32768, 8, 0, W::kStaged},
+        {false, K::kBlock, 2048, 1024, 1 << 20, 256, 0, W::kStaged},  // past one window: in windows
+        {false, K::kBlock, 512, 1024, 32768, 8, 0, W::kStaged},
+        {false, K::kBlock, 512, 1024, 4096 * 32, 32, 0, W::kStaged},       // the longest wave has 32 rounds
+        {false, K::kBlock, 512, 1024, 4096 * 31 + 5, 31, 5, W::kStaged},   // 31 + 1
+        {false, K::kBlock, 512, 1024, 4096 * 32 + 1, 32, 1, W::kHold8},    // 32 + 1 = 33
+        {false, K::kBlock, 512, 1024, 4096 * 33, 33, 0, W::kHold8},
+        {false, K::kBlock, 1024, 1024, kGiB2 / 16 - 1, 131071, 4095, W::kStaged},  // words: 2^31 - 16 bytes
+        {false, K::kBlock, 1024, 1024, kGiB2 / 16, 131072, 0, W::kPerRound},       // words: 2^31 bytes
+        {false, K::kBlock, 2048, 1024, kGiB2 / 8 - 1, 262143, 4095, W::kStaged},
+        {false, K::kBlock, 2048, 1024, kGiB2 / 8, 262144, 0, W::kPerRound},
+        {false, K::kBlock, 512, 1024, kGiB2 / 32, 65536, 0, W::kHold8},
+        {false, K::kBlock, 512, 256, 64, 1, 0, W::kHold8},       // smaller workgroups (lab only) cannot stage
+        {false, K::kBlock, 1024, 512, 64, 1, 0, W::kPerRound},
+        {false, K::kBlock, 2048, 256, 64, 1, 0, W::kPerRound},
+        // compute over a packet stream
+        {false, K::kPitch, 512, 256, 4096, 4, 0, W::kPerRound},
+        {false, K::kPitch, 512, 512, 4097, 2, 1, W::kHold8},
+        {false, K::kPitch, 512, 1024, 1 << 20, 256, 0, W::kHold8},
+        {false, K::kPitch, 512, 256, 1, 0, 1, W::kPerRound},
+        {false, K::kPitch, 1024, 256, 4096, 4, 0, W::kPerRound},
+        {false, K::kPitch, 4096, 256, 16, 0, 16, W::kPerRound},
+        {false, K::kPitch, 1024, 512, 4097, 2, 1, W::kPerRound},
+        {false, K::kPitch, 2048, 1024, 1 << 20, 256, 0, W::kPerRound},
+        {false, K::kPitch, 4096, 1024, 1 << 20, 256, 0, W::kPerRound},
+        // compute over a segment list: held with per-lane addresses at bpc 512, at every launch size
+        {false, K::kSeg, 512, 256, 16, 0, 16, W::kHold8},
+        {false, K::kSeg, 512, 1024, 1 << 20, 256, 0, W::kHold8},
+        {false, K::kSeg, 1024, 256, 16, 0, 16, W::kPerRound},
+        {false, K::kSeg, 2048, 512, 8192, 8, 0, W::kPerRound},
+        {false, K::kSeg, 4096, 1024, 1 << 20, 256, 0, W::kPerRound},
+    };
+    for (const Row &r : rows) {
+        const W got = words_policy(r.verify, r.walk, r.bpc, r.tpb, r.units, r.kq, r.kr);
+        CHECK(got == r.want, "verify %d walk %d bpc %d tpb %d units %llu kq %u kr %u: policy %d, want %d", int(r.verify),
+              int(r.walk), r.bpc, r.tpb, (unsigned long long)r.units, r.kq, r.kr, int(got), int(r.want));
+    }
+    // the words of bpc 1024 at exactly 2^31 - 4 bytes: no whole number of rounds gives them (4 words per round),
+    // so the condition itself at the byte: units * 16 < 2^31 holds up to the last round below and not at 2^31
+    static_assert((kGiB2 / 16 - 1) * 16 + 12 == kGiB2 - 4, "the last round's last word ends 4 bytes below 2 GiB");
+    static_assert(kStageMaxRounds(512) == 32 && kStageMaxRounds(1024) == 64 && kStageMaxRounds(2048) == 128, "windows");
+    // what a launch of no known size gets (launch_wave3's other kernel, the segment kernel's only one)
+    static_assert(words_policy(false, K::kBlock, 512, 1024, kAnyUnits, ~0u, 0) == W::kHold8, "");
+    static_assert(words_policy(false, K::kBlock, 1024, 1024, kAnyUnits, ~0u, 0) == W::kPerRound, "");
+    static_assert(words_policy(false, K::kSeg, 512, 1024, kAnyUnits, 0, 0) == W::kHold8, "");
+}
+
 }  // namespace
 
 int main() {
     check_divide();
     check_walks();
     check_routes();
+    check_words();
     if (g_failed) {
         std::printf("launch plan: %d checks failed\n", g_failed);
         return 1;

@@ -1,9 +1,9 @@
 """The round kernel's lane-fold image, checked on the host (CPU suite): tests/native/fold_image.cpp
 restates one 4 KiB round of the kernel's arithmetic (64-byte lane segments, chained slice-by-4 steps
 from 0, lane-specific nibble fold entries, xor over a chunk's lanes) and compares every chunk with the
-byte-at-a-time SWCrc32c loop (src/common/SWCrc32c.cpp:97-104), for G = 8 / 16 / 32 / 64, both
-polynomials (CRC32C and the CRC-32 of CHECKSUM_CRC32), and both image forms: round 5's, whose
-entries carry each chain's last table step (build_fold_nibbles_pre), and round 4's (lab 157)."""
+byte-at-a-time SWCrc32c loop (src/common/SWCrc32c.cpp:97-104), for G = 8 / 16 / 32 / 64 and both
+polynomials (CRC32C and the CRC-32 of CHECKSUM_CRC32), on the image whose entries carry each chain's
+last table step (build_fold_nibbles_pre)."""
 import os
 import subprocess
 

@@ -346,10 +346,10 @@ def test_wave_split_table():
         "b.kq = uint32_t(units / nwaves);",
         "b.kr = uint32_t(units % nwaves);",
         "if constexpr ((V || PITCH) && TPB == 1024 && (LAB & kLabWg1024) == 0) {",
-        "if (units <= 4096) return launch_wave3<BPC, V, PITCH, SOLO, LAB | kSmall, 256>(a, tab, fold, grid_cap, s);",
+        "if (units <= 4096) return launch_wave3<BPC, V, PITCH, SOLO, LAB, 256, true>(a, tab, fold, grid_cap, s);",
         "if (units <= 16384) return launch_wave3<BPC, V, PITCH, SOLO, LAB, 512>(a, tab, fold, grid_cap, s);",
         "const uint32_t K = a.kq + (wave < a.kr ? 1u : 0u);",
-        "template <int BPC, bool V, bool PITCH, bool SOLO, int LAB = 0, int TPB = kBlockThreads>",
+        "template <int BPC, bool V, bool PITCH, bool SOLO, int LAB = 0, int TPB = kBlockThreads, bool SMALL = false>",
     ]:
         assert squash(line) in wave_h, line
     assert squash("int grid_cap = 256;") in ctx_h

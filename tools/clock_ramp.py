@@ -2,7 +2,7 @@
 """Per-launch shader clock and timing of short regions (why the driver's
 20-launch form runs slower than the steady state). Every launch of the CRC verify (lab variant 125 =
 production + clock stamps) and of the plain stream read records, from workgroup 0, {s_memtime,
-s_memrealtime} at its start and end (LabClock, crc32c_device.h): the shader clock during that
+s_memrealtime} at its start and end (LabClock, crc32c_lab.h): the shader clock during that
 workgroup's life is 100 MHz x d(memtime) / d(realtime), and realtime also places every launch's start.
 
 Phases, each a region of K launches of one 128 MiB block each (8 rotating blocks), HIP events around:

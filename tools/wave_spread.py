@@ -2,7 +2,7 @@
 """Where a 128 MiB launch's time goes, wave by wave (barriered launches at 0.87 of
 the read kernel's per-block rate). Lane 0 of every wave of the stamping kernels (lab variant 125 =
 production verify + LabClock, and the plain stream read) records its realtime start/end (100 MHz),
-its shader clocks and its XCC (LabClock wave buffer, crc32c_device.h). Every wave carries its launch's
+its shader clocks and its XCC (LabClock wave buffer, crc32c_lab.h). Every wave carries its launch's
 number (a kernel argument: no atomics in the stamping path). Per launch:
   gap        previous launch's last wave end -> this launch's first wave start
   ramp       first -> last wave start (dispatch)
