@@ -356,7 +356,26 @@ int32_t hdfs3_output_write(hdfs3_output_stream *s, const void *buf, int32_t len)
  * device (the stream stays usable, nothing was appended); EIO on a failed stream; a failing sink fails
  * the stream as in hdfs3_output_write, after the placements already enqueued have completed. */
 int32_t hdfs3_output_write_dev(hdfs3_output_stream *s, const void *d_buf, int32_t len);
-/* placement launches made by write_dev so far and the bytes it took from device memory; 0 or -errno */
+/* hdfs3_output_write_dev for many device buffers at once (a state dict's tensors): the packets the sink
+ * receives are byte-identical to those of hdfs3_output_write called once per entry, in order, with the same
+ * bytes, and everything said above about tell(), flush, sync, close, block ends, append mode and mixing
+ * holds; write, write_dev and writev_dev share one append accounting. What one call saves over n write_dev
+ * calls is their per-call cost: the entries' ranges share placement launches (one per 64 ranges per batch
+ * touched; hdfs3_gather_sources_dev_async's kernel, which reads no byte outside an entry, so the entries
+ * may be separate allocations of any size and alignment; entries adjacent in memory are placed as one
+ * range), and there is ONE event wait, behind the call's last placement. When the call returns every
+ * source has been read and may be overwritten. Entries with len 0 are skipped (their d_base may be NULL).
+ * Returns the total bytes (0 for n == 0 or only empty entries: nothing is launched), or -1 + errno. Every
+ * argument is checked before anything is appended: EINVAL for NULL, n < 0, a NULL iov with n > 0, a
+ * non-empty entry whose first or last byte is not memory of the stream's device, or a total above
+ * INT64_MAX; the stream stays usable and tell() is unchanged. Otherwise failures are write_dev's. */
+typedef struct hdfs3_dev_iovec {
+    const void *d_base; /* device */
+    uint64_t len;
+} hdfs3_dev_iovec;
+int64_t hdfs3_output_writev_dev(hdfs3_output_stream *s, const hdfs3_dev_iovec *iov, int n);
+/* placement launches made by write_dev / writev_dev so far and the bytes they took from device memory; 0 or
+ * -errno */
 int hdfs3_output_device_stats(hdfs3_output_stream *s, uint64_t *scatter_launches, uint64_t *bytes_from_device);
 int hdfs3_output_flush(hdfs3_output_stream *s);    /* hdfsFlush / hdfsHFlush: flushInternal(false) */
 int hdfs3_output_sync(hdfs3_output_stream *s);     /* hdfsSync: flushInternal(true)               */

@@ -307,6 +307,23 @@ typedef struct hdfs3_copy_range {
 } hdfs3_copy_range;
 int hdfs3_gather_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len,
                            const hdfs3_copy_range *ranges, size_t n);
+/* The gather with a source per range: n ranges, each from a device buffer of its own (a state dict's
+ * tensors), into d_dst. The same kernel and the same contract as hdfs3_gather_dev_async (ctx stream, nothing
+ * waits, ranges[] consumed before return, none of the ctx's staging so any thread may call it, launches
+ * counted in hdfs3_crc_ctx_kernel_launches, 64 ranges per launch, empty ranges dropped, a range that
+ * continues its predecessor in source ADDRESS and destination copied as part of it), with one difference:
+ * a range's source buffer is the range itself. No byte outside [d_src, d_src + len) of any range is read,
+ * whatever lies next to it, so the sources may be separate allocations of any size and alignment.
+ * -EINVAL (before any launch) for a null ctx, null ranges with n > 0, a null d_dst while any range is
+ * non-empty, a non-empty range with a null d_src, a range outside dst_len, or d_src + len wrapping.
+ * Whether the sources are device memory is not checked. */
+typedef struct hdfs3_src_range {
+    const void *d_src; /* first byte (device) */
+    uint64_t dst_off;  /* first byte in d_dst */
+    uint64_t len;      /* bytes               */
+} hdfs3_src_range;
+int hdfs3_gather_sources_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const hdfs3_src_range *ranges,
+                                   size_t n);
 /* Guarded delivery: the gather behind a verify's result word, with the order "verify before copy" kept on
  * the DEVICE. hdfs3_deliver_verified_dev_async copies the ranges exactly as hdfs3_gather_dev_async does
  * (byte-exact, no alignment asked, partial lines byte by byte, nothing outside either buffer), but first

@@ -132,6 +132,9 @@ tSize hdfs3_fs_pread_dev(hdfsFS fs, hdfsFile file, void *d_buffer, tSize length,
  * as hdfsWrite (EINVAL also for a pointer that is not that GPU's memory). The source has been read when
  * the call returns and is never written. hdfsWrite and this call may be mixed on one hdfsFile. */
 tSize hdfs3_fs_write_dev(hdfsFS fs, hdfsFile file, const void *d_buffer, tSize length);
+/* The vectored form (hdfs3_output_writev_dev in hdfs3_client.h): n device buffers as if written one
+ * hdfs3_fs_write_dev each, with one wait for all. Returns the total bytes, or -1 + errno as above. */
+int64_t hdfs3_fs_writev_dev(hdfsFS fs, hdfsFile file, const hdfs3_dev_iovec *iov, int n);
 
 #ifdef __cplusplus
 }

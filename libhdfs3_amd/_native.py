@@ -50,6 +50,12 @@ class CopyRange(ctypes.Structure):
     _fields_ = [("src_off", c_uint64), ("dst_off", c_uint64), ("len", c_uint64)]
 
 
+class SrcRange(ctypes.Structure):
+    """hdfs3_src_range (include/hdfs3_crc.h)."""
+
+    _fields_ = [("d_src", c_void_p), ("dst_off", c_uint64), ("len", c_uint64)]
+
+
 class DeliverGuard(ctypes.Structure):
     """hdfs3_deliver_guard (include/hdfs3_crc.h)."""
 
@@ -102,6 +108,7 @@ PUBLIC_API = {
     "hdfs3_crc32c_compute_packet_stream_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(PktStream),
                                                              c_uint32]),
     "hdfs3_gather_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(CopyRange), c_size_t]),
+    "hdfs3_gather_sources_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(SrcRange), c_size_t]),
     "hdfs3_deliver_verified_dev_async": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, POINTER(CopyRange),
                                                  c_size_t, POINTER(DeliverGuard)]),
     "hdfs3_crc32c_verify_packets_gather_dev": (c_int, [c_void_p, c_void_p, c_size_t, POINTER(PktDesc), c_size_t,
@@ -214,6 +221,12 @@ class AppendInfo(ctypes.Structure):
     _fields_ = [("file_length", c_int64), ("last_block_bytes", c_int64)]
 
 
+class DevIovec(ctypes.Structure):
+    """hdfs3_dev_iovec (include/hdfs3_client.h)."""
+
+    _fields_ = [("d_base", c_void_p), ("len", c_uint64)]
+
+
 class PipelineOpts(ctypes.Structure):
     """hdfs3_pipeline_opts (include/hdfs3_client.h)."""
 
@@ -268,6 +281,7 @@ CLIENT_API = {
     "hdfs3_output_open": (c_int, [POINTER(WriterOpts), PACKET_SINK, c_void_p, POINTER(c_void_p)]),
     "hdfs3_output_write": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
     "hdfs3_output_write_dev": (ctypes.c_int32, [c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_output_writev_dev": (c_int64, [c_void_p, POINTER(DevIovec), c_int]),
     "hdfs3_output_device_stats": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     "hdfs3_output_flush": (c_int, [c_void_p]),
     "hdfs3_output_sync": (c_int, [c_void_p]),
@@ -320,6 +334,7 @@ HDFS_API = {
     "hdfs3_fs_read_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32]),
     "hdfs3_fs_pread_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32, c_int64]),
     "hdfs3_fs_write_dev": (ctypes.c_int32, [c_void_p, c_void_p, c_void_p, ctypes.c_int32]),
+    "hdfs3_fs_writev_dev": (c_int64, [c_void_p, c_void_p, POINTER(DevIovec), c_int]),
     "hdfs3_fs_set_append_stamp": (c_int, [c_void_p, ctypes.c_char_p, c_uint64]),
     "hdfs3_fs_set_block_size": (c_int, [c_void_p, ctypes.c_char_p, ctypes.c_int64]),
 }

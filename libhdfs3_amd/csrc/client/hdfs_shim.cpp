@@ -524,6 +524,14 @@ tSize hdfs3_fs_write_dev(hdfsFS fs, hdfsFile file, const void *d_buffer, tSize l
     return length;
 }
 
+int64_t hdfs3_fs_writev_dev(hdfsFS fs, hdfsFile file, const hdfs3_dev_iovec *iov, int n) {
+    PARAMETER_ASSERT(fs && file && n >= 0 && (iov || n == 0), -1, EINVAL);
+    PARAMETER_ASSERT(!file->input, -1, EINVAL);
+    const int64_t total = hdfs3_output_writev_dev(file->out, iov, n);
+    if (total < 0) return stream_failed(int64_t(-1));
+    return total;
+}
+
 int hdfsFlush(hdfsFS fs, hdfsFile file) {
     PARAMETER_ASSERT(fs && file, -1, EINVAL);
     return hdfsHFlush(fs, file);

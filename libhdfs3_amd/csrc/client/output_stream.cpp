@@ -22,6 +22,11 @@
 // former, runs the same packet compute over the arena, and copies the latter back into the pinned arena
 // with the CRC words, so emit() and the sink see host packets as before. A batch without placed bytes
 // issues exactly the one upload it always did.
+//
+// hdfs3_output_writev_dev is write_dev over a list of device buffers: every entry goes through the same
+// append loop, the ranges it notes carry their source ADDRESS, and a batch's ranges (of however many entries)
+// are placed by the gather with a source per range, 64 to a launch; the one event wait is behind the call's
+// last launch.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -118,7 +123,8 @@ struct hdfs3_output_stream {
     Pkt *cur = nullptr;              // packet being filled (last slot of batch[cur_batch])
     uint64_t packets = 0, batches = 0;
 
-    // write_dev: the current call's source and its ranges into batch[cur_batch] not yet launched
+    // write_dev: the current call's source and its ranges into batch[cur_batch] not yet launched. writev_dev:
+    // no one source (dev_src null), a range's src_off is its source address
     const uint8_t *dev_src = nullptr;
     uint64_t dev_src_len = 0;
     std::vector<CopyRange> dev_pending;
@@ -172,8 +178,10 @@ struct hdfs3_output_stream {
     int place_pending() {
         if (dev_pending.empty()) return 0;
         unsigned launched = 0;
-        const int rc = gather_dev(ctx, batch[cur_batch].a.buf.d, crc_region, dev_src, dev_src_len, dev_pending.data(),
-                                  dev_pending.size(), &launched);
+        uint8_t *arena = batch[cur_batch].a.buf.d;
+        const int rc = dev_src ? gather_dev(ctx, arena, crc_region, dev_src, dev_src_len, dev_pending.data(),
+                                            dev_pending.size(), &launched)
+                               : gather_sources_dev(ctx, arena, crc_region, dev_pending.data(), dev_pending.size(), &launched);
         dev_pending.clear();
         dev_launches += launched;
         if (launched) dev_enqueued = true;
@@ -188,6 +196,30 @@ struct hdfs3_output_stream {
         HIP_OK(hipEventRecord(dev_done, ctx->stream));
         HIP_OK(hipEventSynchronize(dev_done));
         return 0;
+    }
+
+    int need_dev_event() {
+        if (!dev_done) HIP_OK(hipEventCreateWithFlags(&dev_done, hipEventDisableTiming));
+        return 0;
+    }
+
+    // The end of a write_dev / writev_dev call whose appends gave rc: the ranges still noted are launched and
+    // the call's placements waited for. Also after a failure in the middle (a failing sink): the placements
+    // already enqueued still read the source, so they complete before the caller gets it back.
+    int end_dev_call(int rc, std::string *msg) {
+        if (!rc) rc = place_pending();
+        if (rc) *msg = error ? error_msg : std::string(hdfs3_crc_last_error());
+        const int wrc = wait_placed();
+        if (wrc && !rc) {
+            rc = wrc;
+            *msg = hdfs3_crc_last_error();
+        }
+        dev_pending.clear();
+        dev_src = nullptr;
+        dev_src_len = 0;
+        // ranges the ledger counts as placed may never have been launched: the stream cannot go on
+        if (rc && !error) sticky(rc, *msg);
+        return rc;
     }
 
     int dispatch(WBatch &b) {
@@ -332,8 +364,8 @@ struct hdfs3_output_stream {
         return 0;
     }
 
-    // appendInternal (:298-346). dev: buf is device memory (write_dev); only where the bytes are copied
-    // differs, the accounting is this one loop for both
+    // appendInternal (:298-346). dev: buf is device memory (write_dev, writev_dev); only where the bytes are
+    // copied differs, the accounting is this one loop for all three
     int append(const uint8_t *buf, int64_t size, bool dev = false) {
         int64_t todo = size;
         while (todo > 0) {
@@ -349,7 +381,9 @@ struct hdfs3_output_stream {
             const uint32_t n = uint32_t(std::min({todo, pkt_room, blk_room}));
             const uint64_t at = cur->data_off + cur->data_len;
             if (dev) {
-                dev_pending.push_back(CopyRange{uint64_t(size - todo), at, n});
+                // offset in dev_src, or (writev_dev: no dev_src) the address itself
+                dev_pending.push_back(CopyRange{uint64_t(reinterpret_cast<uintptr_t>(buf) + uint64_t(size - todo) -
+                                                         reinterpret_cast<uintptr_t>(dev_src)), at, n});
                 batch[cur_batch].ledger.device(at, n);
             } else {
                 std::memcpy(batch[cur_batch].a.buf.h + at, buf + (size - todo), n);
@@ -515,33 +549,41 @@ int32_t hdfs3_output_write_dev(hdfs3_output_stream *s, const void *d_buf, int32_
     if (!is_device_memory_of(s->ctx, d_buf))
         return posix_fail(EINVAL, "hdfs3_output_write_dev: the buffer is not device memory of device " +
                                       std::to_string(s->ctx->device));
-    if (!s->dev_done) {
-        const hipError_t e = hipEventCreateWithFlags(&s->dev_done, hipEventDisableTiming);
-        if (e != hipSuccess) return posix_fail(EIO, std::string("hipEventCreateWithFlags: ") + hipGetErrorString(e));
-    }
+    if (s->need_dev_event()) return posix_fail(EIO, hdfs3_crc_last_error());
     s->dev_src = static_cast<const uint8_t *>(d_buf);
     s->dev_src_len = uint64_t(len);
-    int rc = s->append(s->dev_src, len, true);
-    if (!rc) rc = s->place_pending();
     std::string msg;
-    if (rc) msg = s->error ? s->error_msg : std::string(hdfs3_crc_last_error());
-    // also after a failure in the middle (a failing sink): the placements already enqueued still read the
-    // source, so they are waited for before the caller gets it back
-    const int wrc = s->wait_placed();
-    if (wrc && !rc) {
-        rc = wrc;
-        msg = hdfs3_crc_last_error();
-    }
-    s->dev_pending.clear();
-    s->dev_src = nullptr;
-    s->dev_src_len = 0;
-    if (rc) {
-        // ranges the ledger counts as placed may never have been launched: the stream cannot go on
-        if (!s->error) s->sticky(rc, msg);
-        return posix_fail(-rc, msg);
-    }
+    if (int rc = s->end_dev_call(s->append(s->dev_src, len, true), &msg)) return posix_fail(-rc, msg);
     s->dev_bytes += uint64_t(len);
     return len;
+}
+
+int64_t hdfs3_output_writev_dev(hdfs3_output_stream *s, const hdfs3_dev_iovec *iov, int n) {
+    if (!s || n < 0 || (n > 0 && !iov)) return posix_fail(EINVAL, "hdfs3_output_writev_dev: invalid argument");
+    if (s->error) return posix_fail(EIO, s->error_msg);
+    DeviceGuard g(s->ctx->device);
+    uint64_t total = 0;
+    for (int i = 0; i < n; ++i) {  // every entry before anything is appended
+        const uint64_t len = iov[i].len;
+        if (!len) continue;
+        const uintptr_t b = reinterpret_cast<uintptr_t>(iov[i].d_base);
+        if (!b || !is_device_memory_of(s->ctx, iov[i].d_base) ||
+            (len > 1 && !is_device_memory_of(s->ctx, reinterpret_cast<const void *>(b + (len - 1)))))
+            return posix_fail(EINVAL, "hdfs3_output_writev_dev: entry " + std::to_string(i) +
+                                          " is not device memory of device " + std::to_string(s->ctx->device));
+        if (len > uint64_t(INT64_MAX) - total)
+            return posix_fail(EINVAL, "hdfs3_output_writev_dev: more than INT64_MAX bytes");
+        total += len;
+    }
+    if (!total) return 0;
+    if (s->need_dev_event()) return posix_fail(EIO, hdfs3_crc_last_error());
+    int rc = 0;
+    for (int i = 0; i < n && !rc; ++i)
+        if (iov[i].len) rc = s->append(static_cast<const uint8_t *>(iov[i].d_base), int64_t(iov[i].len), true);
+    std::string msg;
+    if ((rc = s->end_dev_call(rc, &msg))) return posix_fail(-rc, msg);
+    s->dev_bytes += total;
+    return int64_t(total);
 }
 
 int hdfs3_output_device_stats(hdfs3_output_stream *s, uint64_t *scatter_launches, uint64_t *bytes_from_device) {

@@ -19,6 +19,11 @@
 // one by one, each tested against the buffer. A buffer resource's range check cannot serve here: it
 // drops a 16-byte load whole when its last byte is out of range, and the bytes before it are needed.
 //
+// The gather with a source per range (the kernel's third instantiation; the output stream's vectored write
+// from device memory) is the same copy with each range's src_off an ADDRESS and the range its own source
+// buffer: the bound above then holds per range, so nothing next to a caller's tensor is ever read, at the
+// price of at most two byte-loaded lines per range.
+//
 // The guarded delivery (the kernel's second instantiation) is the same copy behind a verify's result
 // word: it reads that word and a chain word on the device, clips every range to the limit they give
 // (launch_plan.h: deliver_limit) and leaves the chain word for the next delivery, so verify -> copy ->
@@ -33,6 +38,8 @@ namespace hdfs3crc {
 namespace {
 
 typedef uint32_t u32x4g __attribute__((ext_vector_type(4)));
+// a source address out of the kernel arguments read as a global one (a pointer made from an integer is flat)
+#define HDFS3_GLOBAL __attribute__((address_space(1)))
 
 // bytes k .. k+15 of the 32 bytes {lo, hi}, k = 4 j + b
 __device__ __forceinline__ u32x4g shift_quads(const u32x4g lo, const u32x4g hi, uint32_t j, uint32_t b) {
@@ -52,14 +59,16 @@ __device__ __forceinline__ u32x4g shift_quads(const u32x4g lo, const u32x4g hi, 
     return o;
 }
 
-// One kernel, two instantiations. Without a guard argument (launch_gather) it is the plain gather. With one
+// One kernel, three instantiations. Without a guard argument (launch_gather) it is the plain gather. With one
 // (launch_deliver: Guard = DeliverGuard) it is the guarded delivery, the same copy behind a verify's result
 // word: every workgroup reads the two guard words itself (uniform loads, once) and derives the limit, a source
 // offset at which every range ends, so the copy is ordered behind the verify on the device and the host never
 // reads the result in between. One lane of the launch leaves the chain word for the next delivery; gate_out
 // aliases neither word read here (checked by the host), since other workgroups of the launch may still be
 // reading them. A delivery with g.n == 0 only passes the gate on.
-template <typename... Guard>
+// kOwnSource (launch_gather_sources): src and src_len are unused, a range's src_off is its source address
+// and [src_off, src_off + len) the only bytes its workgroups may load.
+template <bool kOwnSource, typename... Guard>
 __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *dst, uint64_t dst_len, const uint8_t *src,
                                                                        uint64_t src_len, const GatherLaunch g,
                                                                        const Guard... guard) {
@@ -92,7 +101,22 @@ __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *
         if (c.len == 0) return;
     }
 
-    const uint64_t src_b = reinterpret_cast<uint64_t>(src), src_e = src_b + src_len;
+    uint64_t src_b = reinterpret_cast<uint64_t>(src);
+    if constexpr (kOwnSource) {
+        src_b = c.src_off;
+        src_len = c.len;
+        c.src_off = 0;
+    }
+    const uint64_t src_e = src_b + src_len;  // every load below is tested against [src_b, src_e)
+    auto load_quad = [&](uint64_t a) -> u32x4g {
+        if constexpr (kOwnSource) return *reinterpret_cast<const HDFS3_GLOBAL u32x4g *>(a);
+        // addressed through the kernel's pointer arguments, so the accesses are global, not flat
+        else return *reinterpret_cast<const u32x4g *>(src + (a - src_b));
+    };
+    auto load_byte = [&](uint64_t a) -> uint8_t {
+        if constexpr (kOwnSource) return *reinterpret_cast<const HDFS3_GLOBAL uint8_t *>(a);
+        else return src[a - src_b];
+    };
     const uint64_t dst_b = reinterpret_cast<uint64_t>(dst), dst_e = dst_b + dst_len;
     const uint64_t D = dst_b + c.dst_off, S = src_b + c.src_off;  // the range's first bytes
     // the range's bytes, clipped once more to the destination buffer (the planner checked them already)
@@ -113,10 +137,8 @@ __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *
         fast[i] = line[i] >= d_lo && line[i] + 16 <= d_hi && q >= src_b && q + (k ? 32 : 16) <= src_e;
         qlo[i] = qhi[i] = u32x4g{0, 0, 0, 0};
         if (fast[i]) {
-            // addressed through the kernel's pointer arguments, so the accesses are global, not flat
-            const u32x4g *sq = reinterpret_cast<const u32x4g *>(src + (q - src_b));
-            qlo[i] = sq[0];
-            if (k) qhi[i] = sq[1];
+            qlo[i] = load_quad(q);
+            if (k) qhi[i] = load_quad(q + 16);
         }
     }
 #pragma unroll
@@ -130,7 +152,7 @@ __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *
         const uint64_t a1 = line[i] + 16 < d_hi ? line[i] + 16 : d_hi;
         for (uint64_t a = a0; a < a1; ++a) {
             const uint64_t s = a + delta;
-            if (s >= src_b && s < src_e) dst[a - dst_b] = src[s - src_b];
+            if (s >= src_b && s < src_e) dst[a - dst_b] = load_byte(s);
         }
     }
 }
@@ -140,7 +162,7 @@ __global__ __launch_bounds__(kGatherThreads) void gather_ranges_kernel(uint8_t *
 hipError_t launch_deliver(hipStream_t stream, void *d_dst, uint64_t dst_len, const void *d_src, uint64_t src_len,
                           const GatherLaunch &g, const DeliverGuard &guard) {
     if (g.n > kGatherMaxRanges) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gather_ranges_kernel<DeliverGuard>, dim3(g.n ? g.tile_end[g.n - 1] : 1), dim3(kGatherThreads), 0, stream,
+    hipLaunchKernelGGL((gather_ranges_kernel<false, DeliverGuard>), dim3(g.n ? g.tile_end[g.n - 1] : 1), dim3(kGatherThreads), 0, stream,
                        static_cast<uint8_t *>(d_dst), dst_len, static_cast<const uint8_t *>(d_src), src_len, g, guard);
     return hipGetLastError();
 }
@@ -149,8 +171,16 @@ hipError_t launch_gather(hipStream_t stream, void *d_dst, uint64_t dst_len, cons
                          const GatherLaunch &g) {
     if (g.n == 0) return hipSuccess;
     if (g.n > kGatherMaxRanges) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(gather_ranges_kernel<>, dim3(g.tile_end[g.n - 1]), dim3(kGatherThreads), 0, stream,
+    hipLaunchKernelGGL(gather_ranges_kernel<false>, dim3(g.tile_end[g.n - 1]), dim3(kGatherThreads), 0, stream,
                        static_cast<uint8_t *>(d_dst), dst_len, static_cast<const uint8_t *>(d_src), src_len, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_sources(hipStream_t stream, void *d_dst, uint64_t dst_len, const GatherLaunch &g) {
+    if (g.n == 0) return hipSuccess;
+    if (g.n > kGatherMaxRanges) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_ranges_kernel<true>, dim3(g.tile_end[g.n - 1]), dim3(kGatherThreads), 0, stream,
+                       static_cast<uint8_t *>(d_dst), dst_len, static_cast<const uint8_t *>(nullptr), uint64_t(0), g);
     return hipGetLastError();
 }
 

@@ -204,6 +204,9 @@ hipError_t launch_gather(hipStream_t stream, void *d_dst, uint64_t dst_len, cons
 // that only passes the gate on.
 hipError_t launch_deliver(hipStream_t stream, void *d_dst, uint64_t dst_len, const void *d_src, uint64_t src_len,
                           const GatherLaunch &g, const DeliverGuard &guard);
+// The same launch with a source per range (plan_gather_launch over ranges whose src_off is a device ADDRESS,
+// checked by gather_sources_first_bad): a range's loads stay inside [src_off, src_off + len).
+hipError_t launch_gather_sources(hipStream_t stream, void *d_dst, uint64_t dst_len, const GatherLaunch &g);
 
 // HDFS3_LAB=1 builds the measurement library (libhdfs3_crc_lab.so: tools/, the A/B tests):
 // the same production launchers plus a process-wide kernel-variant knob, the kernel

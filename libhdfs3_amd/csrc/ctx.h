@@ -205,6 +205,10 @@ inline LaunchEnv launch_env(hdfs3_crc_ctx *ctx, PieceScratch *own_pieces = nullp
 // calling thread's current device is the ctx's). *launched (if given) is raised by the launches made.
 int gather_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len, const CopyRange *r,
                size_t n, unsigned *launched = nullptr);
+// hdfs3_gather_sources_dev_async without its null checks: gather_dev with a source address per range (r[i].src_off;
+// launch_plan.h: gather_sources_first_bad), the same checks first, the same launches, stream and counter.
+int gather_sources_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const CopyRange *r, size_t n,
+                       unsigned *launched = nullptr);
 // hdfs3_deliver_verified_dev_async without its null checks of ctx and buffers: the guard and every range checked
 // first (-EINVAL before any launch), then gather_dev's launches as guarded deliveries, each reading the same
 // guard words and writing the same chain word; with nothing to copy one launch still passes the gate on.

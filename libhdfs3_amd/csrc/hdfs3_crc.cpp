@@ -385,6 +385,23 @@ int gather_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_sr
     return 0;
 }
 
+int gather_sources_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const CopyRange *r, size_t n, unsigned *launched) {
+    const size_t bad = gather_sources_first_bad(r, n, dst_len);
+    if (bad != n)
+        return fail(-EINVAL, "range %zu lies outside the %zu-byte destination or its source wraps", bad, dst_len);
+    for (size_t i = 0; i < n; ++i)
+        if (r[i].len && (!d_dst || !r[i].src_off)) return fail(-EINVAL, "range %zu: null buffer", i);
+    GatherLaunch g;
+    for (size_t pos = 0; pos < n;) {
+        pos = plan_gather_launch(reinterpret_cast<uintptr_t>(d_dst), r, n, pos, &g);
+        if (g.n == 0) continue;  // nothing but empty ranges
+        HIP_TRY(launch_gather_sources(ctx->stream, d_dst, dst_len, g));
+        ++ctx->launches;
+        if (launched) ++*launched;
+    }
+    return 0;
+}
+
 int deliver_dev(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len, const CopyRange *r,
                 size_t n, const DeliverGuard &guard, unsigned *launched) {
     if (!guard.result) return fail(-EINVAL, "null result word");
@@ -570,6 +587,21 @@ int hdfs3_gather_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, cons
     if (!d_dst || !d_src || !ranges) return fail(-EINVAL, "null buffer");
     DeviceGuard g(ctx->device);
     return gather_dev(ctx, d_dst, dst_len, d_src, src_len, reinterpret_cast<const CopyRange *>(ranges), n);
+}
+
+static_assert(sizeof(hdfs3_src_range) == sizeof(CopyRange) && sizeof(const void *) == sizeof(uint64_t) &&
+                  offsetof(hdfs3_src_range, d_src) == offsetof(CopyRange, src_off) &&
+                  offsetof(hdfs3_src_range, dst_off) == offsetof(CopyRange, dst_off) &&
+                  offsetof(hdfs3_src_range, len) == offsetof(CopyRange, len),
+              "a source range is a copy range whose src_off is the source address");
+
+int hdfs3_gather_sources_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const hdfs3_src_range *ranges,
+                                   size_t n) {
+    if (!ctx) return fail(-EINVAL, "null hdfs3_crc_ctx");
+    if (n == 0) return 0;
+    if (!ranges) return fail(-EINVAL, "null ranges");
+    DeviceGuard g(ctx->device);
+    return gather_sources_dev(ctx, d_dst, dst_len, reinterpret_cast<const CopyRange *>(ranges), n);
 }
 
 int hdfs3_deliver_verified_dev_async(hdfs3_crc_ctx *ctx, void *d_dst, size_t dst_len, const void *d_src, size_t src_len,

@@ -206,6 +206,11 @@ size_t gather_first_bad(const CopyRange *in, size_t n, uint64_t src_len, uint64_
     return n;
 }
 
+size_t gather_sources_first_bad(const CopyRange *in, size_t n, uint64_t dst_len) {
+    // the address space as the one source buffer: a range inside it does not wrap
+    return gather_first_bad(in, n, ~uint64_t(0), dst_len);
+}
+
 size_t plan_gather_launch(uint64_t dst_addr, const CopyRange *in, size_t n, size_t pos, GatherLaunch *g) {
     g->n = 0;
     uint64_t tiles = 0;  // of the ranges before the last one

@@ -196,6 +196,12 @@ size_t gather_first_bad(const CopyRange *in, size_t n, uint64_t src_len, uint64_
 // sides merged into it, closed at kGatherMaxRanges ranges or kGatherMaxTiles tiles. g->n may be 0 (nothing
 // but empty ranges were left). The ranges were checked by gather_first_bad.
 size_t plan_gather_launch(uint64_t dst_addr, const CopyRange *in, size_t n, size_t pos, GatherLaunch *g);
+// The gather with a source per range (mirrors hdfs3_src_range): src_off is the range's source ADDRESS and the
+// range its own source buffer. plan_gather_launch plans such a list as it stands (a range merges into a
+// predecessor it continues in address and destination; the merged range is again its own source). Index of
+// the first range that leaves [0, dst_len), whose src_off + len wraps, or that has more than kGatherMaxTiles
+// tiles; n when there is none.
+size_t gather_sources_first_bad(const CopyRange *in, size_t n, uint64_t dst_len);
 
 // ---- guarded delivery (crc32c_gather.hip: the gather behind a verify's result word) -----------------
 // A delivery copies ranges as the gather does, each clipped to a LIMIT (a source offset) that the kernel

@@ -286,6 +286,15 @@ class CrcContext:
               self._lib.hdfs3_gather_dev_async(self.ctx, d_dst, dst_len, d_src, src_len, self._ranges(ranges),
                                                len(ranges)))
 
+    def gather_sources_dev(self, d_dst: int, dst_len: int, ranges) -> None:
+        """hdfs3_gather_sources_dev_async: ranges = [(src_ptr, dst_off, len)], each range read from a device
+        buffer of its own; enqueued on the ctx stream."""
+        arr = (_native.SrcRange * max(len(ranges), 1))()
+        for i, (src_ptr, dst_off, n) in enumerate(ranges):
+            arr[i].d_src, arr[i].dst_off, arr[i].len = src_ptr, dst_off, n
+        self._check("hdfs3_gather_sources_dev_async",
+              self._lib.hdfs3_gather_sources_dev_async(self.ctx, d_dst, dst_len, arr, len(ranges)))
+
     def deliver_verified_dev(self, d_dst: int, dst_len: int, d_src: int, src_len: int, ranges, *, d_result: int,
                              bpc: int, granule: int, data_off: int = 0, chunk_base: int = 0,
                              d_gate_in: int | None = None, d_gate_out: int | None = None) -> None:
@@ -716,6 +725,20 @@ class OutputStream:
         """hdfs3_output_write_dev: hdfsWrite of the n bytes at the device address d_ptr (memory of the
         stream's device). The source has been read when the call returns."""
         return self._posix("hdfs3_output_write_dev", self._lib.hdfs3_output_write_dev(self.s, d_ptr, n))
+
+    @staticmethod
+    def dev_iovec(entries) -> ctypes.Array:
+        """[(ptr, n), ...] as a hdfs3_dev_iovec array (built once by callers that time the call)."""
+        arr = (_native.DevIovec * max(len(entries), 1))()
+        for i, (ptr, n) in enumerate(entries):
+            arr[i].d_base, arr[i].len = ptr, n
+        return arr
+
+    def writev_device(self, entries) -> int:
+        """hdfs3_output_writev_dev: entries = [(ptr, n), ...], device buffers written one after the other as
+        by write_device, with one wait for all. Every source has been read when the call returns."""
+        return self._posix("hdfs3_output_writev_dev",
+                           self._lib.hdfs3_output_writev_dev(self.s, self.dev_iovec(entries), len(entries)))
 
     def device_stats(self):
         from ctypes import c_uint64
